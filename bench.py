@@ -16,11 +16,20 @@ Default workload = config C5 (BASELINE.json): the deterministic synthetic
 10M-triangle sphere field at 3840x2160, octree traversal.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5|c4|c3|c2|c1]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line (value, ms_per_step, the step's own HIP-event kernel times).  --full
+adds every measurement that takes runs of its own: the instrumented pass
+behind the roofline object, the committed PMC profiles, the fresh-camera
+loop and the CPU baseline.  --dump-outputs DIR writes what the last timed
+step computed (the assembled image and the frame's query counts) as .npy.
 
 Prints ONE JSON line on rank 0 (plus progress on stderr).
 """
 import argparse
+import collections
 import ctypes
 import gzip
 import json
@@ -244,6 +253,28 @@ def frame_checked(ctx, rank, world, frame, steps, what, fatal=True):
     return (float(t[1].item()), None) if not fatal else float(t[1].item())
 
 
+DUMP_PIXELS = 4_000_000  # 48 MB of f32 RGB: the --dump-outputs cap on the image
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(path, rgb, W, H, closest, shadow):
+    """--dump-outputs: what a caller of the timed step receives, from the
+    last timed step.  image.npy: the assembled PPM-order f32 image, (H, W, 3),
+    or -- above DUMP_PIXELS pixels -- the (DUMP_PIXELS, 3) rows of a fixed
+    sample of its pixels (ascending flat indices drawn without replacement
+    by numpy's default_rng(DUMP_SEED), the same for every run of a size).
+    queries.npy: the frame's closest-hit and shadow query counts (f64)."""
+    os.makedirs(path, exist_ok=True)
+    img = rgb.view(H * W, 3)
+    if H * W > DUMP_PIXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, DUMP_PIXELS, replace=False))
+        img = img[torch.from_numpy(idx).to(img.device)].cpu().numpy()
+    else:
+        img = img.cpu().numpy().reshape(H, W, 3)
+    np.save(os.path.join(path, "image.npy"), img)
+    np.save(os.path.join(path, "queries.npy"), np.array([closest, shadow], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -251,6 +282,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="c5", choices=sorted(WORKLOADS))
     ap.add_argument("--accel", default=None, choices=["flat", "octree", "octree_gpu"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the instrumented pass and the "
+                         "committed PMC profiles (roofline, sq), the fresh-camera loop (--camera-pan) "
+                         "and the CPU baseline (--cpu-seconds, --cpu-threads, --no-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's image (a fixed seeded pixel "
+                         "sample above 4M pixels) and query counts to DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
                     help="CPU baseline budget (split between Mode A and Mode B)")
     ap.add_argument("--cpu-threads", type=int, default=None,
@@ -285,6 +323,8 @@ def main():
     ap.add_argument("--valu-json", default=None,
                     help="PMC summary (tools/gpu_profile.sh pmc_sq.json, SQ counters) to report as sq")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -329,9 +369,11 @@ def main():
     sh = stream.cuda_stream
     assert sh, "expected a non-null HIP stream handle"
 
-    # instrumented pass (untimed): algorithmic work per frame for the roofline
-    ctx.set_count_work(True)
-    for attempt in range(2):
+    # instrumented pass (untimed, --full only): algorithmic work per frame for
+    # the roofline; a plain run leaves every count at 0 and reports none
+    work = collections.defaultdict(int)
+    ctx.set_count_work(args.full)
+    for attempt in range(2 if args.full else 0):
         ctx.render(frame, rank, world, tiles.data_ptr(), sh)
         try:
             work = ctx.stats()
@@ -381,21 +423,31 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    retry = 0
+    # a plain run without warm-up has rendered nothing yet: one untimed step
+    # sizes the hit-record buffer and counts the frame's queries
+    retry = 0 if args.warmup > 0 or args.full else 1
     try:
-        st = ctx.stats()
+        st = None if retry else ctx.stats()
     except rtgpu.RtError as e:  # the first frame sized the hit-record buffer: once more
         if e.code != -10:
             raise
         retry = 1
-    # every rank steps again if any rank must (step() holds a collective)
-    flag = torch.tensor([retry], dtype=torch.int32, device=dev)
-    if world > 1:
-        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-    if int(flag.item()):
+    # every rank steps again if any rank must (step() holds a collective);
+    # twice only where the first of these steps was the first frame ever
+    for attempt in range(2):
+        flag = torch.tensor([retry], dtype=torch.int32, device=dev)
+        if world > 1:
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        if not int(flag.item()):
+            break
         step()
         torch.cuda.synchronize()
-        st = ctx.stats()
+        try:
+            st = ctx.stats()
+            retry = 0
+        except rtgpu.RtError as e:
+            if e.code != -10 or attempt or args.warmup > 0 or args.full:
+                raise
     assert st["depth_overflow"] == 0 and st["shadow_unproven"] == 0
     counts = torch.tensor([st["closest"], st["shadow"], st["hits"], st["pixels"],
                            work["node_visits"], work["tri_tests"], work["hits"],
@@ -433,6 +485,47 @@ def main():
     # never printed for a timed region with an incomplete or unproven frame
     timed_q = frame_checked(ctx, rank, world, frame, args.steps, "timed")
     ctx.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rgb, W, H, closest, shadow)
+
+    if not args.full:
+        # the headline line alone: the value and the step's own event times
+        # (triangle-parallel lists: the produce / all-to-all / consume wall time)
+        lists_ms = sum(part_ms) / len(part_ms) if part_ms else sum(a for a, _ in ft) / len(ft)
+        tt = torch.tensor([el, lists_ms, sum(b for _, b in ft) / len(ft)] +
+                          [sum(k[i] for k in kt) / len(kt) for i in range(3)], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        el, lists_ms, kern_ms, trace_ms, shade_ms, fold_ms = tt.tolist()
+        if abs(timed_q - (closest + shadow) * args.steps) > 0.5:
+            raise SystemExit(f"timed frames made {timed_q:.0f} queries, {(closest + shadow) * args.steps:.0f} "
+                             "expected (the same frame every step): no value printed")
+        if rank == 0:
+            print(json.dumps({
+                "metric": "Mrays/sec (primary+shadow) at 3840x2160",
+                "value": round(timed_q / el / 1e6, 3),
+                "unit": "Mrays/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(el / args.steps * 1e3, 3),
+                "higher_is_better": True,
+                "scaling": "strong",
+                "vs_baseline": None,
+                "dtype": "f32",
+                "data": "synthetic" if wl["kind"] == "synthetic" else f"reference scene {wl['scene']}.svati",
+                "config": {"workload": wl["desc"], "width": W, "height": H, "triangles": ntri,
+                           "accel": wl["accel"],
+                           "queries_per_frame": {"closest": int(closest), "shadow": int(shadow),
+                                                 "closest_hits": int(hits), "pixels": int(pixels)}},
+                "kernel_ms": {"candidate_lists": round(lists_ms, 3), "render": round(kern_ms, 3),
+                              "trace": round(trace_ms, 3), "shade": round(shade_ms, 3),
+                              "fold": round(fold_ms, 3)},
+                "full": False,
+            }), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # the same number of frames again, each with a new camera (panned
     # --camera-pan pixels per step): a one-shot render or an animation

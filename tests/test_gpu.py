@@ -1196,8 +1196,39 @@ def test_camera_refine_on_off(gpu, accel):
             assert v["filter_violation"] == 0, (on, nranks, rank, v)
 
 
+def test_bench_plain_run_dumps_outputs(gpu, scene_dir, tmp_path):
+    """A plain bench.py run (no --full): the headline line alone, --steps
+    timed steps, and --dump-outputs' image.npy / queries.npy equal to the
+    same frame rendered through render_image, bit for bit."""
+    import json
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--workload", "c1",
+                        "--steps", "2", "--warmup", "0", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mrays/sec (primary+shadow) at 3840x2160" and d["unit"] == "Mrays/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 0 and d["value"] > 0 and d["ms_per_step"] > 0
+    for k in ("roofline", "cpu_baseline", "fresh_camera", "ms_per_step_fresh", "sq"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path / "out")) == ["image.npy", "queries.npy"]
+    img = np.load(tmp_path / "out" / "image.npy")
+    q = np.load(tmp_path / "out" / "queries.npy")
+    s = gpu.Scene.load_svati(os.path.join(scene_dir, "cube.svati"))
+    s.set_size(256, 256)
+    ref, st = gpu.Context(s, "flat").render_image(s.frame())
+    assert img.dtype == np.float32 and q.dtype == np.float64
+    assert_bitexact(img, ref, "bench.py --dump-outputs image")
+    assert q.tolist() == [st["closest"], st["shadow"]]
+    assert d["config"]["queries_per_frame"]["closest"] == st["closest"]
+    # value = queries / time; the line rounds ms_per_step to 0.001 ms of a step of ~0.1 ms: within 1 %
+    assert abs(d["value"] - (st["closest"] + st["shadow"]) / d["ms_per_step"] / 1e3) <= 1e-2 * d["value"]
+
+
 def test_bench_json_contract(gpu, tmp_path):
-    """bench.py as the driver runs it (one GPU, a small workload, a short CPU
+    """bench.py --full as the driver runs it (one GPU, a small workload, a short CPU
     baseline): one JSON line on stdout with the contract's fields -- the
     metric and unit, whole-job value, per-step times (replay and fresh
     camera), the roofline object of the dominant kernel and the CPU baseline
@@ -1206,7 +1237,7 @@ def test_bench_json_contract(gpu, tmp_path):
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", "c1", "--steps", "3",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--workload", "c1", "--steps", "3",
                         "--warmup", "1", "--cpu-seconds", "2", "--cpu-threads", "2"],
                        capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]

@@ -8,7 +8,7 @@ OUT=gpurun_out/${TAG:-bench_all}
 mkdir -p "$OUT"
 run() {  # name, bench args...
   local name=$1; shift
-  timeout -k 10 300 python3 bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || exit $?
+  timeout -k 10 300 python3 bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || exit $?
   python3 -c "import json; d=json.load(open('$OUT/$name.json')); print('$name', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
 }
 run c1 --workload c1 --steps 20 --warmup 2 --cpu-seconds 16

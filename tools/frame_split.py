@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-frame kernel times from a rocprofv3 kernel trace of bench.py (not part
+"""Per-frame kernel times from a rocprofv3 kernel trace of bench.py --full (not part
 of the product): frames are split at each trace_kernel dispatch (a frame's
 list kernels come before its trace), and the kernels of the last N frames
 (bench's fresh-camera loop) are compared with the N before them (the timed

@@ -13,10 +13,10 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout
 rc=$?; tail -3 "$OUT/pytest.log"; echo "pytest rc=$rc"
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-    -- python3 bench.py --no-cpu --steps 5 --warmup 1 > "$OUT/trace.log" 2>&1 || exit $?
+    -- python3 bench.py --full --no-cpu --steps 5 --warmup 1 > "$OUT/trace.log" 2>&1 || exit $?
 echo traced
 for e in ${SLACKS:-64}; do
-  timeout -k 10 200 python bench.py --no-cpu --steps 10 --warmup 2 --camera-slack $e \
+  timeout -k 10 200 python bench.py --full --no-cpu --steps 10 --warmup 2 --camera-slack $e \
       > "$OUT/cs_$e.json" 2> "$OUT/cs_$e.err" || exit $?
   echo "slack $e done"
 done

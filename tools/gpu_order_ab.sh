@@ -15,7 +15,7 @@ for v in default ${VARIANTS:-}; do
   [ $v = default ] || lib=raytracing-gpu_amd/lib/var_$v/librtgpu.so
   RTGPU_LIB=$lib timeout -k 10 300 python3 tools/rank_share.py --nranks ${NR:-8} --all-ranks --steps 5 \
       --out $O/rs_$v.json > $O/rs_$v.log 2>&1 || { tail -20 $O/rs_$v.log; exit 1; }
-  RTGPU_LIB=$lib timeout -k 10 200 python3 bench.py --no-cpu --steps 10 --warmup 2 > $O/bench_$v.json 2> $O/bench_$v.err \
+  RTGPU_LIB=$lib timeout -k 10 200 python3 bench.py --full --no-cpu --steps 10 --warmup 2 > $O/bench_$v.json 2> $O/bench_$v.err \
       || { tail -20 $O/bench_$v.err; exit 1; }
   python3 - $O/rs_$v.json $O/bench_$v.json $v <<'PY'
 import json, sys

@@ -19,7 +19,7 @@ mkdir -p "$OUT"
 # the device code these passes measure (bench.py reports a profile's counters
 # only for the tree whose device_code_hash() matches)
 python3 -c "import sys; sys.argv=['x']; sys.path.insert(0, '.'); import bench; print(bench.device_code_hash())" > "$OUT/device_hash.txt"
-B="bench.py --workload $WL ${BENCH_EXTRA:-}"
+B="bench.py --full --workload $WL ${BENCH_EXTRA:-}"
 echo "== kernel trace"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
     -- python3 $B --no-cpu --steps 5 --warmup 1 > "$OUT/trace.log" 2>&1

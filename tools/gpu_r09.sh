@@ -15,7 +15,7 @@ if [ -z "${NO_TESTS:-}" ]; then
 fi
 i=0
 for args in ${BENCHES:-"--steps 20 --warmup 3 --no-cpu"}; do :; done
-IFS=';' read -ra BL <<< "${BENCHES:---steps 20 --warmup 3 --no-cpu}"
+IFS=';' read -ra BL <<< "${BENCHES:---full --steps 20 --warmup 3 --no-cpu}"
 for args in "${BL[@]}"; do
   i=$((i+1))
   timeout -k 10 ${BENCH_TIMEOUT:-300} python bench.py $args > $OUT/bench$i.json 2> $OUT/bench$i.err

@@ -10,7 +10,7 @@ T=${1:?tag}; O=gpurun_out/$T; mkdir -p $O
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -40 $O/pytest.log; exit 1; }
 tail -1 $O/pytest.log
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
-timeout -k 10 200 python3 bench.py --steps 10 --warmup 2 > $O/bench_c5.json 2> $O/bench_c5.err || { tail -20 $O/bench_c5.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 2 > $O/bench_c5.json 2> $O/bench_c5.err || { tail -20 $O/bench_c5.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench_c5.json')); r=d['roofline']; print('C5', d['ms_per_step'], 'ms', d['value'], 'Mrays/s; trace', r['kernels']['trace']['ms'], 'shade', r['kernels']['shade']['ms'], 'lists', r['candidate_lists_ms'])"
 [ "${SCALING:-1}" = 1 ] || exit 0
 timeout -k 10 500 python3 tools/rank_share.py --nranks 1 2 4 8 --all-ranks --partition --steps 3 --out $O/rank_share.json > $O/rank_share.log 2>&1 || { tail -20 $O/rank_share.log; exit 1; }

@@ -12,7 +12,7 @@ timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 $O/pytest.log
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 200 python3 bench.py > $O/bench_c5.json 2> $O/bench_c5.err || { tail -20 $O/bench_c5.err; exit 1; }
+timeout -k 10 200 python3 bench.py --full > $O/bench_c5.json 2> $O/bench_c5.err || { tail -20 $O/bench_c5.err; exit 1; }
 TAG=${T}_val/all timeout -k 10 900 bash tools/bench_all.sh || exit 1
 TAG=${T}_c5 timeout -k 10 1200 bash tools/gpu_profile.sh > $O/profile.log 2>&1 || { tail -20 $O/profile.log; exit 1; }
 tail -3 $O/profile.log

@@ -10,5 +10,5 @@ export TMPDIR=/tmp
 out=$1; shift
 ctr=$1; shift
 timeout -s KILL 300 rocprofv3 --pmc $ctr -d "$out" -o pmc --output-format csv \
-    -- python3 bench.py --no-cpu --steps 2 --warmup 0 "$@" > "$out.log" 2>&1
+    -- python3 bench.py --full --no-cpu --steps 2 --warmup 0 "$@" > "$out.log" 2>&1
 python3 tools/pmc_reduce.py "$out" -o "$out.json"

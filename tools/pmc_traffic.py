@@ -2,9 +2,9 @@
 """Per-launch HBM traffic of each render kernel from rocprofv3 --pmc passes.
 
     rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o fetch --output-format csv \\
-        -- python3 bench.py --no-cpu ...
+        -- python3 bench.py --full --no-cpu ...
     rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write -o write --output-format csv \\
-        -- python3 bench.py --no-cpu ...
+        -- python3 bench.py --full --no-cpu ...
     python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write -o profiles/x.json
 
 FETCH_SIZE / WRITE_SIZE are in KiB (rocprofv3 derived counters), taken from
