@@ -672,6 +672,11 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
       c->known.valid = c->kept_for.valid = 0;
       c->kept_pending = 0;
     } else if (c->known.valid) {
+      // the counters are those of the frame the snapshot was taken for
+      // (kept_pend: set with snap_pending, below), not of the read-back frame
+      // known still names: that one rendered again must not match them as its
+      // own exact shape -- it is one more new camera, sized with headroom
+      c->known.set(&c->kept_pend.frame, c->kept_pend.rank, c->kept_pend.nranks);
       c->known.total = h[6];
       c->known.nglobal = h[1];
       c->known.nbig = h[2];

@@ -31,6 +31,12 @@ PROBE = os.path.join(REPO, "oracle", "_ref", "rt_probe")
 SMALL = (96, 54)
 # (scene, W, H): the small sweep over every reference scene, plus config C1.
 EXTRA = [("cube", 256, 256), ("triangle", 64, 64), ("island_smooth", 192, 108)]
+# Ragged frames: widths and heights that are no multiple of the 8x8 tile, tall
+# frames, frames of a single partial tile.  98x50 leaves a 2x2 corner tile (4
+# camera rays in a wave) and 13x7 tiles (ragged in 4x4 tile blocks too).
+RAGGED_SCENES = ("island_smooth", "spheres", "car-on-road")
+RAGGED = ([(s, w, h) for w, h in ((98, 50), (100, 52), (54, 96)) for s in RAGGED_SCENES]
+          + [("island_smooth", w, h) for w, h in ((6, 130), (250, 2), (2, 2), (30, 34))])
 
 
 def rewrite_camera(src, dst, w, h):
@@ -82,7 +88,7 @@ def main():
     if not os.path.exists(PROBE):
         sys.exit("build the reference probe first: make -C oracle ref")
     scenes = sorted(f[:-6] for f in os.listdir(REF_TESTS) if f.endswith(".svati"))
-    cases = [(s, *SMALL) for s in scenes] + EXTRA
+    cases = [(s, *SMALL) for s in scenes] + EXTRA + RAGGED
     with cf.ThreadPoolExecutor(args.jobs) as ex:
         results = list(ex.map(lambda c: run_case(*c), cases))
     with open(os.path.join(HERE, "manifest.json"), "w") as f:

@@ -67,7 +67,10 @@ def test_tile_ownership_is_a_partition():
 
 
 @pytest.mark.parametrize("W,H,n", [(96, 54, 2), (96, 54, 3), (192, 108, 8), (3840, 2160, 8),
-                                   (3840, 2160, 7), (1920, 1080, 3), (40, 24, 5)])
+                                   (3840, 2160, 7), (1920, 1080, 3), (40, 24, 5),
+                                   # ragged: partial tile columns and rows, tall frames, one partial tile
+                                   (100, 52, 3), (98, 50, 8), (10, 6, 2), (2, 2, 1), (54, 96, 4),
+                                   (30, 34, 2), (6, 130, 8), (250, 2, 5)])
 def test_tile_map_partitions_the_frame(built, W, H, n):
     """Every pixel belongs to exactly one (rank, tile-buffer slot); the host
     mirror's sizes agree with the library's (rt_hip_tiles_per_rank); every
@@ -97,7 +100,9 @@ def test_tile_map_partitions_the_frame(built, W, H, n):
 
 
 @pytest.mark.parametrize("W,H,n", [(96, 54, 2), (96, 54, 3), (192, 108, 8), (480, 272, 8),
-                                   (3840, 216, 8), (3840, 216, 7), (40, 24, 5)])
+                                   (3840, 216, 8), (3840, 216, 7), (40, 24, 5),
+                                   (100, 52, 3), (98, 50, 8), (10, 6, 2), (2, 2, 1), (54, 96, 4),
+                                   (30, 34, 2), (6, 130, 8), (250, 2, 5)])
 def test_tile_map_row_arithmetic(built, W, H, n):
     """The O(1) row counts and run-order emission of csrc/rt_tiles.h (the
     candidate lists' per-row tile counts, emit_interval and kth_rank_col

@@ -89,7 +89,7 @@ def test_candidate_survey_reference_scene(scene_dir):
     assert r["safe"] + r["footprint"] + r["global"] == s.triangle_count
 
 
-@pytest.mark.parametrize("case", ["small", "c5"])
+@pytest.mark.parametrize("case", ["small", "c5", "474x266", "266x476"])
 def test_tile_refinement_drops_only_tiles_the_reference_never_accepts(case):
     """The per-tile refinement of the camera candidate lists (csrc/rt_cand.hip
     tile_keep) drops a (triangle, tile) entry only where its proof says no
@@ -101,8 +101,13 @@ def test_tile_refinement_drops_only_tiles_the_reference_never_accepts(case):
     headline scene, every 200th refined entry."""
     import rtgpu
     import oracle as orc
+    ragged = "x" in case
     if case == "small":
         s = rtgpu.Scene.synthetic(4, 4, 1200, seed=0x5EED, width=480, height=270)
+        stride = 1
+    elif ragged:  # a partial last tile column (and row): fewer rays behind tile_keep's bound
+        W, H = (int(x) for x in case.split("x"))
+        s = rtgpu.Scene.synthetic(4, 4, 1200, seed=0x5EED, width=W, height=H)
         stride = 1
     else:
         s = rtgpu.Scene.synthetic(32, 32, 9776, seed=0x5EED, width=3840, height=2160)
@@ -111,6 +116,8 @@ def test_tile_refinement_drops_only_tiles_the_reference_never_accepts(case):
     assert len(rows) == total > 0
     drop = rows[:, 3] == 0
     assert drop.sum() > 0 and (~drop).sum() > 0
+    if ragged:  # (the oracle clips the 8x8 rectangles to the frame)
+        assert W % 8 and (rows[:, 1] == (W - 1) // 8).sum() > 0
     tris = s.triangles_array()
     rects = np.stack([rows[:, 2] * 8, rows[:, 1] * 8, np.full(len(rows), 8), np.full(len(rows), 8)], 1)
     acc = orc.camera_tri_accepts(s.ptr, tris[rows[:, 0]], rects)
@@ -118,14 +125,10 @@ def test_tile_refinement_drops_only_tiles_the_reference_never_accepts(case):
     assert int((acc[~drop, 0] > 0).sum()) > 0  # real hits live in kept tiles
 
 
-def test_tile_refinement_compat_drops_only_never_accepted_tiles():
-    """test_tile_refinement_drops_only_tiles_the_reference_never_accepts for
-    the gpu/rt compatibility mode's lists (one ray per pixel of the 3x frame,
-    gpu/raytracer.cu:97-103; tile_keep's compat sample rectangle), checked
-    with the oracle's restatement of those rays."""
+def _compat_refinement(W, H):
     import rtgpu
     import oracle as orc
-    s = rtgpu.Scene.synthetic(4, 4, 1200, seed=0x5EED, width=160, height=90)
+    s = rtgpu.Scene.synthetic(4, 4, 1200, seed=0x5EED, width=W, height=H)
     rows, total = rtgpu.cand_refine_sample(s, stride=1, cap=1 << 20, compat=True)
     assert len(rows) == total > 0
     drop = rows[:, 3] == 0
@@ -135,3 +138,20 @@ def test_tile_refinement_compat_drops_only_never_accepted_tiles():
     acc = orc.camera_tri_accepts(s.ptr, tris[rows[:, 0]], rects, gpu=True)
     assert int(acc[drop, 1].max()) == 0, rows[drop][acc[drop, 1] > 0][:8]
     assert int((acc[~drop, 0] > 0).sum()) > 0
+    return rows
+
+
+def test_tile_refinement_compat_drops_only_never_accepted_tiles():
+    """test_tile_refinement_drops_only_tiles_the_reference_never_accepts for
+    the gpu/rt compatibility mode's lists (one ray per pixel of the 3x frame,
+    gpu/raytracer.cu:97-103; tile_keep's compat sample rectangle), checked
+    with the oracle's restatement of those rays."""
+    _compat_refinement(160, 90)
+
+
+def test_tile_refinement_compat_partial_tile_column():
+    """The same at 158x90: the 3x frame is 474 wide, so its last tile column
+    holds 2 of 8 pixel columns -- and refined entries, some of them dropped on
+    the proof for those rays alone."""
+    rows = _compat_refinement(158, 90)
+    assert (3 * 158) % 8 and (rows[:, 1] == (3 * 158 - 1) // 8).sum() > 0

@@ -802,6 +802,73 @@ def test_async_lists_new_cameras(gpu):
             (st_ref["closest"], st_ref["shadow"], st_ref["cand_entries"])
 
 
+def _survey_entries(gpu, scene, du):
+    """Host-only: the candidate-list entries of the scene's frame with the eye
+    panned by du (rtgpu.cand_survey takes the camera from the scene)."""
+    f0 = scene.frame()
+    u = np.array([f0.u.x, f0.u.y, f0.u.z], np.float64)
+    u /= np.linalg.norm(u)
+    pos = scene.s.camera.position
+    keep = (pos.x, pos.y, pos.z)
+    pos.x, pos.y, pos.z = (float(keep[k] + u[k] * du) for k in range(3))
+    try:
+        return gpu.cand_survey(scene)["entries"]
+    finally:
+        pos.x, pos.y, pos.z = keep
+
+
+@pytest.mark.parametrize("rank,nranks", [(0, 1), (1, 4)])
+def test_async_lists_revisited_cameras(gpu, rank, nranks):
+    """A viewer that pans away and back: A, B+, A, B-, A, B+, B+, A on one
+    context (A the scene's camera, B+- near pans).  The counters an
+    estimated-shape build (a new camera) reports belong to that camera: A
+    rendered again after B must not be built as if B's entry total, launch
+    shape and over-cap flag were its own exact sizes -- with fewer entries in
+    B than in A that was a spurious RT_EHITBUF (rt_lists.cpp cand_prepare).
+    Every render returns, and equals the read-back build of a fresh context
+    for its camera: the rank's tiles bit for bit (the whole frame as rank 0 of
+    1), and the counts.
+    Then a far jump and back (A, pan 3.0, A): RT_EHITBUF is allowed there (the
+    estimate legitimately outgrown), the immediate retry must succeed, and
+    every render that returns success is complete and bit-exact."""
+    s = gpu.Scene.synthetic(4, 4, 1200, seed=0x5EED, width=480, height=270)
+    du = 0.05
+    n_a, n_p, n_m = (_survey_entries(gpu, s, d) for d in (0.0, du, -du))
+    assert min(n_p, n_m) < n_a, (n_a, n_p, n_m)  # A needs more than the B whose counts it would inherit
+    frames = {"A": s.frame(), "B+": _panned_frame(gpu, s, du), "B-": _panned_frame(gpu, s, -du),
+              "far": _panned_frame(gpu, s, 3.0)}
+
+    def render(ctx, f):
+        # rt_hip_render + rt_hip_stats themselves (rt_hip_render_image renders
+        # again on RT_EHITBUF, which would hide a spurious one)
+        return _tiles_of_rank(ctx, f, rank, nranks)
+
+    refs = {k: render(gpu.Context(s, "octree_gpu"), f) for k, f in frames.items()}
+    assert refs["A"][1]["cand_entries"] > 0
+
+    def check(k, img, st, what):
+        ref, st_ref = refs[k]
+        assert_bitexact(img, ref, what)
+        assert (st["closest"], st["shadow"], st["cand_entries"]) == \
+            (st_ref["closest"], st_ref["shadow"], st_ref["cand_entries"]), what
+
+    ctx = gpu.Context(s, "octree_gpu")
+    for i, k in enumerate(("A", "B+", "A", "B-", "A", "B+", "B+", "A")):
+        try:
+            img, st = render(ctx, frames[k])
+        except gpu.RtError as e:
+            pytest.fail(f"render {i} (camera {k}), rank {rank}/{nranks}: {e}")
+        check(k, img, st, f"render {i} (camera {k}), rank {rank}/{nranks}")
+    ctx = gpu.Context(s, "octree_gpu")
+    for i, k in enumerate(("A", "far", "A")):
+        try:
+            img, st = render(ctx, frames[k])
+        except gpu.RtError as e:
+            assert e.code == -10 and i > 0, (i, k, e.code)  # RT_EHITBUF, on a transition only
+            img, st = render(ctx, frames[k])  # the retry reads its sizes back
+        check(k, img, st, f"far jump, render {i} (camera {k}), rank {rank}/{nranks}")
+
+
 def test_triangle_parallel_lists_two_processes(gpu):
     """Two processes (ranks of torch.distributed.run, both on GPU 0, gloo
     for the exchange since RCCL needs a device per rank): each produces its
@@ -1261,3 +1328,259 @@ def test_bench_json_contract(gpu, tmp_path):
         assert k in cpu, k
     assert cpu["kind"] == "port" and cpu["cores"] == 2 and cpu["value"] > 0
     assert cpu["sample_pixels_bitexact_vs_gpu"] is True
+
+
+# ------------------------------------------------------- ragged frame sizes
+# Frames whose width is no multiple of the 8x8 tile (partial tile columns),
+# tall frames and frames of one partial tile: the reference's goldens
+# (tests/golden/make_golden.py RAGGED).  test_golden_bitexact and
+# test_golden_exact_reflections render them too (they take every manifest
+# case); these tests reach the code that only such sizes run -- camera waves
+# of fewer than kPacketMin lanes, the column half of the validity mask, lists
+# clipped to partial tiles, padded blocks in a rank split.
+RAGGED = [c for c in CASES if c["width"] % 8]
+RAGGED_IDS = [case_id(c) for c in RAGGED]
+
+
+def _ragged_case(scene, W, H):
+    return next(c for c in RAGGED if (c["scene"], c["width"], c["height"]) == (scene, W, H))
+
+
+def _ragged_scene(gpu, scene_dir, case):
+    s = gpu.Scene.load_svati(os.path.join(scene_dir, case["scene"] + ".svati"))
+    s.set_size(case["width"], case["height"])
+    return s
+
+
+def test_ragged_cases_are_the_planned_ones():
+    sizes = {(98, 50), (100, 52), (54, 96)}
+    want = {(sc, w, h) for (w, h) in sizes for sc in ("island_smooth", "spheres", "car-on-road")}
+    want |= {("island_smooth", w, h) for (w, h) in ((6, 130), (250, 2), (2, 2), (30, 34))}
+    assert {(c["scene"], c["width"], c["height"]) for c in RAGGED} == want
+
+
+def _assert_lists_match_host(v, what):
+    assert v["fp_mismatch"] == 0 and v["tile_mismatch"] == 0 and v["filter_violation"] == 0, (what, v)
+
+
+@pytest.mark.parametrize("accel", ["octree", "octree_gpu"])
+@pytest.mark.parametrize("case", RAGGED, ids=RAGGED_IDS)
+def test_ragged_candidate_lists_match_host(gpu, scene_dir, case, accel):
+    """The device-built camera candidate lists of a ragged frame (footprints
+    clamped to the last, partial tile; the per-tile refinement over a partial
+    tile's own rays) equal the host re-derivation: no footprint mismatch, no
+    differing tile, no fast-path filter violation -- and the render they feed
+    is the golden.  98x50 (13 x 7 tiles, ragged in 4 x 4 blocks) also as
+    ranks 0 and 2 of 3."""
+    s = _ragged_scene(gpu, scene_dir, case)
+    f = s.frame()
+    ctx = gpu.Context(s, accel)
+    img, st = ctx.render_image(f)
+    assert_bitexact(img, golden_image(case), f"{case_id(case)}/{accel}")
+    _assert_lists_match_host(ctx.cand_verify(f), f"{case_id(case)}/{accel}")
+    if (case["width"], case["height"]) == (98, 50):
+        gold = golden_image(case)
+        for rank in (0, 2):
+            t, _ = _tiles_of_rank(ctx, f, rank, 3)
+            assert_bitexact(t, gpu.tiles_from_image_numpy(gold, rank, 3)[: len(t)], f"rank {rank}/3 tiles")
+            _assert_lists_match_host(ctx.cand_verify(f, rank, 3), f"{case_id(case)}/{accel} rank {rank}/3")
+
+
+@pytest.mark.parametrize("trav", [1, 2, 3])
+def test_ragged_traversal_policies_bitexact(gpu, scene_dir, trav):
+    """98x50 (a 2x2 corner tile: 4 camera rays in a wave) and 2x2 (nothing
+    else) under every traversal policy: 2 forces the staged packet walk onto
+    the 4-lane waves, 1 the per-lane walk onto the full tiles, the default
+    (every other test) and 3 mix them by lane count.  All give the golden's
+    bits and query counts."""
+    for case in RAGGED:
+        if (case["width"], case["height"]) not in ((98, 50), (2, 2)):
+            continue
+        s = _ragged_scene(gpu, scene_dir, case)
+        ctx = gpu.Context(s, "octree")
+        ctx.set_policy(trav)
+        img, st = ctx.render_image(s.frame())
+        assert_bitexact(img, golden_image(case), f"{case_id(case)} trav {trav}")
+        assert (st["closest"], st["shadow"]) == (case["closest"], case["shadow"]), (case_id(case), trav)
+
+
+@pytest.mark.parametrize("accel", ["octree", "octree_gpu"])
+def test_ragged_shadow_queries_match_brute_force(gpu, scene_dir, accel):
+    """Every shadow query of the 98x50 car-on-road frame equals brute force
+    over all triangles on the same hit records."""
+    case = _ragged_case("car-on-road", 98, 50)
+    s = _ragged_scene(gpu, scene_dir, case)
+    ctx = gpu.Context(s, accel)
+    img, st = ctx.render_image(s.frame())
+    assert_bitexact(img, golden_image(case), f"{case_id(case)}/{accel}")
+    v = ctx.verify_shadows(1)
+    assert v["records"] > 0 and v["queries"] > 0, v
+    assert v["records_differ"] == 0 and v["walk_lit_brute_shadowed"] == 0, v
+
+
+@pytest.mark.parametrize("nranks", [2, 3, 8])
+@pytest.mark.parametrize("W,H", [(98, 50), (54, 96), (30, 34), (250, 2)])
+def test_ragged_rank_split_gather_assemble(gpu, scene_dir, W, H, nranks):
+    """Rank-sharded renders of a ragged frame (tile buffers prefilled with
+    NaN) + rank-major gather + the device assemble == the golden, with the
+    golden's summed query counts; every slot of a rank's buffer that is
+    padding (a pixel or a whole tile of a padded block past the frame's
+    edge, rtgpu.tile_pixels' -1) is written as 0.0; a rank that owns no tile
+    (30x34 is 1 x 2 blocks: six of 8 ranks) succeeds with zero counts and
+    contributes nothing (its NaNs never reach the image).  250x2 over 8 ranks:
+    8 x 1 blocks, every rank exactly one."""
+    import ctypes as C
+    case = _ragged_case("island_smooth", W, H)
+    s = _ragged_scene(gpu, scene_dir, case)
+    f = s.frame()
+    ctx = gpu.Context(s, "octree")
+    per = gpu.tile_buffer_floats(W, H, nranks)
+    counts = [gpu.rank_tile_count(W, H, r, nranks) for r in range(nranks)]
+    assert per == 192 * max(counts)
+    if (W, H, nranks) == (30, 34, 8):
+        assert sorted(counts) == [0] * 6 + [16, 16]
+    if (W, H, nranks) == (250, 2, 8):
+        assert counts == [16] * 8
+    L = gpu.lib()
+    dg, drgb = C.c_void_p(), C.c_void_p()
+    assert L.rt_hip_malloc(0, per * nranks * 4, C.byref(dg)) == 0
+    assert L.rt_hip_malloc(0, W * H * 12, C.byref(drgb)) == 0
+    host = np.full(per * nranks, np.nan, np.float32)
+    assert L.rt_hip_memcpy_h2d(dg, host.ctypes.data_as(C.c_void_p), host.nbytes) == 0
+    nan_img = np.full((H, W, 3), np.nan, np.float32)
+    assert L.rt_hip_memcpy_h2d(drgb, nan_img.ctypes.data_as(C.c_void_p), nan_img.nbytes) == 0
+    tot = {"closest": 0, "shadow": 0, "pixels": 0}
+    for r in range(nranks):
+        ctx.render(f, r, nranks, dg.value + r * per * 4)  # raises unless RT_OK
+        st = ctx.stats()
+        if counts[r] == 0:
+            assert (st["closest"], st["shadow"], st["pixels"]) == (0, 0, 0), (r, st)
+        for k in tot:
+            tot[k] += st[k]
+    ctx.assemble(f, dg.value, nranks, drgb.value)
+    img = np.empty((H, W, 3), np.float32)
+    ctx.stats()  # sync
+    assert L.rt_hip_memcpy_d2h(img.ctypes.data_as(C.c_void_p), drgb, img.nbytes) == 0
+    assert L.rt_hip_memcpy_d2h(host.ctypes.data_as(C.c_void_p), dg, host.nbytes) == 0
+    L.rt_hip_free(dg)
+    L.rt_hip_free(drgb)
+    gold = golden_image(case)
+    assert_bitexact(img, gold, f"{case_id(case)}: {nranks} ranks assembled")
+    assert (tot["closest"], tot["shadow"]) == (case["closest"], case["shadow"])
+    bufs = host.reshape(nranks, -1, 64, 3)
+    for r in range(nranks):
+        if counts[r] == 0:  # nothing of an empty rank's buffer is written
+            assert np.isnan(bufs[r]).all(), f"rank {r}/{nranks} owns no tile but wrote"
+            continue
+        pix = gpu.tile_pixels(W, H, r, nranks)
+        assert len(pix) == counts[r]
+        mine = bufs[r, : len(pix)]
+        pad = pix[..., 0] < 0
+        assert (mine[pad].view(np.uint32) == 0).all(), f"rank {r}/{nranks}: padding slots not 0.0"
+        assert_bitexact(mine[~pad], gold[pix[..., 0][~pad], pix[..., 1][~pad]], f"rank {r}/{nranks} tiles")
+        # past the rank's own tiles nothing is written
+        assert np.isnan(bufs[r, len(pix):]).all(), f"rank {r}/{nranks}: wrote past its tiles"
+
+
+@pytest.mark.parametrize("W,H", [(98, 50), (54, 96)])
+@pytest.mark.parametrize("scene", ["island_smooth", "spheres", "car-on-road"])
+def test_ragged_cli_ppm_md5(gpu, scene_dir, tmp_path, scene, W, H):
+    """`rt file.svati out.ppm` writes the reference's exact bytes at ragged sizes."""
+    case = _ragged_case(scene, W, H)
+    sv = tmp_path / f"{scene}_{W}x{H}.svati"
+    _with_camera_size(os.path.join(scene_dir, scene + ".svati"), sv, W, H)
+    out = tmp_path / "o.ppm"
+    exe = os.path.join(REPO, "raytracing-gpu_amd", "lib", "rt")
+    subprocess.run([exe, str(sv), str(out)], check=True, timeout=120)
+    assert hashlib.md5(out.read_bytes()).hexdigest() == case["ppm_md5"]
+
+
+@pytest.mark.parametrize("nranks", [3, 8])
+def test_ragged_raytrace_multi_ranks_on_one_gpu(gpu, scene_dir, tmp_path, nranks):
+    """rt_raytrace_multi_dev (per-rank octrees and renders, the gather and
+    the assemble skipping the padded blocks' tiles) at 98x50 -- 13 tile
+    columns, not a multiple of the 4-tile blocks, and a partial last one --
+    with every rank on device 0 writes the reference's exact bytes."""
+    for scene in ("island_smooth", "spheres", "car-on-road"):
+        case = _ragged_case(scene, 98, 50)
+        sv = tmp_path / f"{scene}_98x50.svati"
+        _with_camera_size(os.path.join(scene_dir, scene + ".svati"), sv, 98, 50)
+        out = tmp_path / f"{scene}.ppm"
+        st, _ = gpu.raytrace_devices(str(sv), str(out), [0] * nranks)
+        assert hashlib.md5(out.read_bytes()).hexdigest() == case["ppm_md5"], (scene, nranks)
+        assert (st["closest"], st["shadow"]) == (case["closest"], case["shadow"]), (scene, nranks)
+
+
+_REFINED_REF = {}
+
+
+def _refined_reference(gpu, W, H):
+    """Per size, once: the synthetic scene, its brute-force frame and counts,
+    and 64 oracle pixels -- 8 of them in the last (partial) tile column, 8 in
+    the last (partial) tile row."""
+    if (W, H) not in _REFINED_REF:
+        import oracle as orc
+        s = gpu.Scene.synthetic(4, 4, 1200, seed=0x5EED, width=W, height=H)
+        img_f, st_f = gpu.Context(s, "flat").render_image(s.frame())
+        rng = np.random.default_rng(17)
+        pix = np.stack([rng.integers(0, H, 64), rng.integers(0, W, 64)], axis=1).astype(np.int32)
+        pix[:8, 1] = rng.integers(8 * ((W - 1) // 8), W, 8)
+        pix[8:16, 0] = rng.integers(8 * ((H - 1) // 8), H, 8)
+        vals, _ = orc.render(s.ptr, W, H, pixels=pix, threads=0)
+        _REFINED_REF[(W, H)] = (s, img_f, st_f, pix, vals)
+    return _REFINED_REF[(W, H)]
+
+
+@pytest.mark.parametrize("accel", ["octree_gpu", "octree"])
+@pytest.mark.parametrize("W,H", [(474, 266), (266, 476)])
+def test_ragged_refined_lists_on_device(gpu, W, H, accel):
+    """The smallest frames found whose per-tile refinement (tile_keep) has
+    entries in a partial tile column (2 of 8 pixel columns; rows: 2 resp. 4 of
+    8), wide and tall: the octree render with those lists == brute force bit
+    for bit with equal counts, the lists == the host re-derivation, and
+    sampled pixels -- the partial column and row among them -- == the oracle."""
+    s, img_f, st_f, pix, vals = _refined_reference(gpu, W, H)
+    assert W % 8 and H % 8
+    assert (pix[:, 1] >= 8 * ((W - 1) // 8)).sum() >= 8 and (pix[:, 0] >= 8 * ((H - 1) // 8)).sum() >= 8
+    f = s.frame()
+    ctx = gpu.Context(s, accel)
+    img, st = ctx.render_image(f)
+    assert st["cand_entries"] > 0
+    assert_bitexact(img, img_f, f"synthetic {W}x{H} {accel} vs brute force")
+    assert (st["closest"], st["shadow"]) == (st_f["closest"], st_f["shadow"])
+    v = ctx.cand_verify(f)
+    assert v["listed"] > 0 and v["entries"] > 0, v
+    _assert_lists_match_host(v, f"synthetic {W}x{H} {accel}")
+    assert_bitexact(img[pix[:, 0], pix[:, 1]], vals, f"synthetic {W}x{H} {accel} vs oracle sample")
+    assert_bitexact(img_f[pix[:, 0], pix[:, 1]], vals, f"synthetic {W}x{H} brute force vs oracle sample")
+
+
+_COMPAT_REF = {}
+
+
+def _compat_reference(scene_dir, scene, W, H):
+    if (scene, W, H) not in _COMPAT_REF:
+        import oracle as orc
+        s = gpu_mod().Scene.load_svati(os.path.join(scene_dir, scene + ".svati"))
+        s.set_size(W, H)
+        _COMPAT_REF[(scene, W, H)] = (s,) + orc.render_gpu(s.ptr, W, H, threads=8)
+    return _COMPAT_REF[(scene, W, H)]
+
+
+@pytest.mark.parametrize("accel", ["flat", "octree", "octree_gpu"])
+@pytest.mark.parametrize("W,H", [(34, 18), (33, 19)])
+@pytest.mark.parametrize("scene", ["spheres", "island_smooth"])
+def test_ragged_compat_matches_oracle(gpu, scene_dir, scene, W, H, accel):
+    """rt_hip_render_compat at camera sizes whose 3x frame is ragged -- 34x18
+    (102x54 rays: 6 of 8 columns in the last tile) and the odd 33x19 (99x57:
+    odd in both directions, which gpu/rt accepts, host/vecmath.c) -- == the
+    oracle's restatement of gpu/ byte for byte with the same query counts, and
+    the octrees' compat candidate lists == the host re-derivation."""
+    s, ref, cnt = _compat_reference(scene_dir, scene, W, H)
+    ctx = gpu.Context(s, accel)
+    img, st = ctx.render_compat(s.camera)
+    bad = np.argwhere((img != ref).any(axis=2))
+    assert len(bad) == 0, f"{scene} {W}x{H} {accel}: {len(bad)} pixels differ, first {bad[:4].tolist()}"
+    assert (st["closest"], st["shadow"]) == (cnt["closest"], cnt["shadow"])
+    if accel != "flat":
+        _assert_lists_match_host(ctx.cand_verify_compat(s.camera), f"{scene} {W}x{H} {accel} compat")
