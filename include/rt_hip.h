@@ -16,6 +16,8 @@
  *                                  (cpu/raytracer.c:19-77), collide/collide_dist/apply_light
  *                                  (cpu/hit.c:72-109, cpu/light.c:33-100) on the device
  *   rt_hip_assemble()    (new)     tile buffers of all ranks -> PPM-order float image
+ *   rt_hip_gbuffer()     (new)     opt-in per-sample passes of the last render: winning
+ *                                  triangle, object, queries, depth, hit point, normal
  *   rt_raytrace_multi()  (new)     in-process 1..8 GPU render + RCCL gather over xGMI
  *
  * Test, tuning and measurement hooks (probes, surveys, verification, A/B
@@ -243,6 +245,47 @@ int rt_hip_assemble(rt_hip_ctx *ctx, const rt_frame *frame, const float *d_gathe
 /* Convenience: single-GPU render of the whole frame into host memory
  * h_rgb (W*H*3 floats, PPM order); synchronous. */
 int rt_hip_render_image(rt_hip_ctx *ctx, const rt_frame *frame, float *h_rgb, rt_stats *stats);
+
+/* Per-sample G-buffer (new; opt-in, default off): what the renderer knows
+ * about each of a pixel's four camera samples beside its colour.  One record
+ * of RT_GB_WORDS 32-bit words per sample, 4 per pixel in cpu sample order:
+ * sample s has k = i + 0.5 (s >> 1), l = j + 0.5 (s & 1) (cpu/raytracer.c:55-58).
+ *   prim     winner of collide() for the camera ray: the global triangle index
+ *            in (object, LIFO triangle) order = the triangle counts of the
+ *            earlier objects + the index into objects[obj].triangles; -1: miss
+ *   obj      the winner's object index; -1: miss
+ *   queries  closest-hit queries of the sample's path: the camera ray, every
+ *            reflection and the final miss (the coef < 0.01 cut-off makes none)
+ *   dist     the winner's new_dist (cpu/hit.c); +inf: miss
+ *   P, N     hit point and interpolated normal, the bits the shading used;
+ *            0 for a miss and for a winner whose interpolated normal is
+ *            exactly zero (counted in rt_stats.zero_normal)
+ * With the G-buffer on, rt_hip_render runs the default trace kernel's
+ * capturing instantiation (16 B more per sample); lists, shading and the
+ * image are unchanged.  It fails with RT_EINVAL together with a non-default
+ * traversal policy, rt_hip_set_count_work or rt_hip_set_exact_reflections;
+ * rt_hip_render_compat captures nothing.  The G-buffer is valid whenever the
+ * image is (after RT_EHITBUF: render again). */
+#define RT_GB_WORDS 10
+typedef struct rt_gsample { int prim, obj, queries; float dist, P[3], N[3]; } rt_gsample;
+int rt_hip_set_gbuffer(rt_hip_ctx *ctx, int enable);
+/* Words of a rank's G-buffer tile buffer: the layout of the colour tile
+ * buffer ("Image tiling" above) with 4 * RT_GB_WORDS words per pixel slot
+ * (sample-major) in place of 3 floats; padding slots are misses of 0 queries. */
+size_t rt_hip_gbuffer_tile_words(int width, int height, int nranks);
+/* The G-buffer tiles of the last rt_hip_render, which must have been of the
+ * same frame, rank and nranks with the G-buffer on, on the same stream (else
+ * RT_EINVAL).  Asynchronous.  A rank without tiles writes nothing. */
+int rt_hip_gbuffer(rt_hip_ctx *ctx, const rt_frame *frame, int rank, int nranks, void *d_tiles,
+                   void *stream);
+/* rt_hip_assemble for G-buffer tile buffers: d_samples receives H*W*4
+ * rt_gsample in PPM pixel order. */
+int rt_hip_assemble_gbuffer(rt_hip_ctx *ctx, const rt_frame *frame, const void *d_gathered, int nranks,
+                            void *d_samples, void *stream);
+/* rt_hip_render_image plus the G-buffer (on for this call only);
+ * h_samples = H*W*4 records, PPM order. */
+int rt_hip_render_image_gbuffer(rt_hip_ctx *ctx, const rt_frame *frame, float *h_rgb,
+                                rt_gsample *h_samples, rt_stats *stats);
 
 /* gpu/rt compatibility mode (gpu/raytracer.cu:31-129,
  * gpu/light.cu, gpu/colors.cu): the camera's frame rendered at 3x width and

@@ -146,12 +146,20 @@ struct rt_hip_ctx {
   size_t hit_need = 0;              // per region: what the last overflowing frame needed
   uint32_t* d_last = nullptr;       // per (item, lane): a path's deepest record
   size_t last_cap = 0;              // items
+  // G-buffer (rt_hip_set_gbuffer): the capturing trace's record per (item,
+  // lane), and the frame whose render filled it (gb_valid: rt_hip_gbuffer may
+  // read it; rank / nranks / stream are last_p's and last_stream)
+  int gbuffer = 0;
+  uint4* d_capture = nullptr;
+  size_t capture_cap = 0;           // items
+  int gb_valid = 0;
+  rt_frame gb_frame{};
 // per-rank candidate lists built without a host read-back (VERDICT r04
 // "render is async"): 1 = on (the first frame still reads its total back)
 #ifndef RT_ASYNC_LISTS_DEFAULT
 #define RT_ASYNC_LISTS_DEFAULT 1
 #endif
-  int grid_of[2][RT_NPOLICIES][2] = {};  // persistent grids [trace][policy][count_work] (4: shade only, 5: trace only)
+  int grid_of[2][RT_NPOLICIES][2] = {};  // persistent grids [trace][policy][count_work] (4: shade only, 5, 6: trace only)
   int cus = 0;                      // compute units of the device
   std::vector<uint32_t> light_type; // per light (rt_hip_verify_shadows)
   std::vector<float> light_v;       // per light: l.v (3 floats)

@@ -53,6 +53,7 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* c) {
   (void)hipFree(c->d_hit_prev);
   (void)hipFree(c->d_hit_term);
   (void)hipFree(c->d_last);
+  (void)hipFree(c->d_capture);
   (void)hipFree(c->d_prim_mu);
   (void)hipFree(c->d_node_mu);
   (void)hipFree(c->d_oob);
@@ -587,7 +588,14 @@ static int hit_buffers(rt_hip_ctx* c, size_t ntiles) {
     HIP_TRY(hipMalloc((void**)&c->d_last, items * 64 * sizeof(uint32_t)));
     c->last_cap = items;
   }
-  size_t want = (2 * items * 64 + RT_HIT_REGIONS - 1) / RT_HIT_REGIONS + 1024;
+  if (c->gbuffer && items > c->capture_cap) {  // the capturing trace's record per (item, lane)
+    (void)hipFree(c->d_capture);
+    c->d_capture = nullptr;
+    c->capture_cap = 0;
+    HIP_TRY(hipMalloc((void**)&c->d_capture, items * 64 * sizeof(uint4)));
+    c->capture_cap = items;
+  }
+  size_t want =(2 * items * 64 + RT_HIT_REGIONS - 1) / RT_HIT_REGIONS + 1024;
   if (c->hit_need > want) want = c->hit_need;
   if (want > (1ull << 29) - 1) want = (1ull << 29) - 1;  // slot field of a record index
   if (want <= c->hit_cap && c->d_hit) return RT_OK;
@@ -617,6 +625,15 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   // model of the candidate lists assumes it (rt_cand.hip pixel_range)
   if ((f->width | f->height) & 1)
     return rt_set_error(RT_EINVAL, "frame %dx%d: cpu/rt renders even sizes only", f->width, f->height);
+  // the G-buffer's capture exists for the default kernels only (its own
+  // trace instantiation, RT_POLICY_GBUFFER): refused before anything changes
+  if (c->gbuffer) {
+    if (c->policy != RT_POLICY_DEFAULT)
+      return rt_set_error(RT_EINVAL, "the G-buffer needs the default traversal policy (have %d)", c->policy);
+    if (c->count_work) return rt_set_error(RT_EINVAL, "the G-buffer cannot be captured by the work-counting pass");
+    if (c->exact_refl) return rt_set_error(RT_EINVAL, "the G-buffer cannot be captured with exact reflections on");
+  }
+  c->gb_valid = 0;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   // lists rt_hip_cand_consume built for exactly this frame and rank: used once
@@ -675,12 +692,17 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     }
     c->last_p = p;
     c->last_stream = s;
+    if (c->gbuffer) {  // rt_hip_gbuffer of this rank writes nothing either
+      c->gb_frame = *f;
+      c->gb_valid = 1;
+    }
     return RT_OK;
   }
   {
     int rc = hit_buffers(c, (size_t)p.ntiles_local);
     if (rc) return rc;
   }
+  if (c->gbuffer) p.capture = c->d_capture;
   p.hit = c->d_hit;
   p.hit_prev = c->d_hit_prev;
   p.hit_term = c->d_hit_term;
@@ -783,6 +805,9 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     p.node_rf = c->d_node_rf;
     tpol = RT_POLICY_EXACT_REFL;
   }
+  // G-buffer: the default trace kernel (octree or FLAT) plus the capture --
+  // its own instantiation; lists, shade, fixup and fold are the default's
+  if (c->gbuffer) tpol = RT_POLICY_GBUFFER;
   int gt = empty ? c->grid : c->grid_of[1][tpol][cw], gs = empty ? c->grid : c->grid_of[0][spol][cw];
   // small frames: no more persistent waves than work items (every wave pulls
   // items until all 8 streams drain, so any grid covers the frame; the
@@ -800,6 +825,7 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     return rt_set_error(RT_EHIP, "render: prim-order records missing");
   if (!p.hit || !p.last || !p.out || (p.nrec && (!p.tri || !p.nrm)))
     return rt_set_error(RT_EHIP, "render: device buffers missing");
+  if (c->gbuffer && !p.capture) return rt_set_error(RT_EHIP, "render: G-buffer capture buffer missing");
   // item clocks for the same frame's next work order (only the candidate
   // lists' order uses them)
   if (p.tile_order && RT_COST_ORDER) {
@@ -836,6 +862,10 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   if (c->timing) HIP_TRY(hipEventRecord(ev[3], s));
   HIP_TRY(rt_launch_fold(&p, s));
   c->last_p = p;
+  if (c->gbuffer) {
+    c->gb_frame = *f;
+    c->gb_valid = 1;
+  }
   if (c->timing) {
     HIP_TRY(hipEventRecord(ev[4], s));
     c->frames++;
@@ -993,6 +1023,99 @@ extern "C" int rt_hip_render_image(rt_hip_ctx* c, const rt_frame* f, float* h_rg
   }
   (void)hipFree(d_tiles);
   (void)hipFree(d_rgb);
+  return rc;
+}
+
+// ----------------------------------------------------------------- G-buffer
+static_assert(RT_GB_WORDS == RT_GB_WORDS_D && sizeof(rt_gsample) == 4 * RT_GB_WORDS,
+              "rt_gsample is the record gbuffer_kernel writes");
+extern "C" int rt_hip_set_gbuffer(rt_hip_ctx* c, int enable) {
+  if (!c) return rt_set_error(RT_EINVAL, "null context");
+  c->gbuffer = enable ? 1 : 0;
+  if (!c->gbuffer) c->gb_valid = 0;
+  return RT_OK;
+}
+
+extern "C" size_t rt_hip_gbuffer_tile_words(int width, int height, int nranks) {
+  return (size_t)rt_hip_tiles_per_rank(width, height, nranks) * 64 * 4 * RT_GB_WORDS;
+}
+
+extern "C" int rt_hip_gbuffer(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, void* d_tiles,
+                              void* stream) {
+  if (!c || !f || !d_tiles) return rt_set_error(RT_EINVAL, "null argument");
+  if ((uintptr_t)d_tiles & 7) return rt_set_error(RT_EINVAL, "G-buffer tiles must be 8-byte aligned");
+  if (!c->gbuffer || !c->gb_valid)
+    return rt_set_error(RT_EINVAL, "no G-buffer capture: rt_hip_set_gbuffer(1), then rt_hip_render");
+  const KParams& lp = c->last_p;
+  if (lp.rank != rank || lp.nranks != nranks || std::memcmp(&c->gb_frame, f, sizeof *f) != 0)
+    return rt_set_error(RT_EINVAL, "the G-buffer holds another frame (last render: %dx%d, rank %d of %d)",
+                        lp.W, lp.H, lp.rank, lp.nranks);
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (s != c->last_stream)
+    return rt_set_error(RT_EINVAL, "the G-buffer must be read on the stream of its render");
+  if (lp.ntiles_local == 0) return RT_OK;  // a rank past the last block: nothing rendered, nothing written
+  HIP_TRY(hipSetDevice(c->device));
+  // every pointer gbuffer_kernel follows (a null one would fault the card)
+  if (!lp.capture || !lp.hit || (lp.nrec && !lp.tri_prim))
+    return rt_set_error(RT_EHIP, "G-buffer: device buffers missing");
+  HIP_TRY(rt_launch_gbuffer(&lp, (uint32_t*)d_tiles, s));
+  return RT_OK;
+}
+
+extern "C" int rt_hip_assemble_gbuffer(rt_hip_ctx* c, const rt_frame* f, const void* d_gathered, int nranks,
+                                       void* d_samples, void* stream) {
+  if (!c || !f || !d_gathered || !d_samples || nranks <= 0) return rt_set_error(RT_EINVAL, "bad argument");
+  if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  HIP_TRY(rt_launch_assemble_words((const uint32_t*)d_gathered, (uint32_t*)d_samples, f->width, f->height,
+                                   tiles_x_of(f->width), nranks,
+                                   rt_hip_tiles_per_rank(f->width, f->height, nranks), 4 * RT_GB_WORDS, s));
+  return RT_OK;
+}
+
+// rt_hip_render_image with the G-buffer on for the call (the context's
+// setting is restored): the image, and the samples in PPM pixel order
+extern "C" int rt_hip_render_image_gbuffer(rt_hip_ctx* c, const rt_frame* f, float* h_rgb,
+                                           rt_gsample* h_samples, rt_stats* st) {
+  if (!c || !f || !h_rgb || !h_samples) return rt_set_error(RT_EINVAL, "null argument");
+  if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nt = rt_hip_tile_buffer_floats(f->width, f->height, 1);
+  const size_t ng = rt_hip_gbuffer_tile_words(f->width, f->height, 1);
+  const size_t npx = (size_t)f->width * f->height;
+  const size_t nsw = npx * 4 * RT_GB_WORDS;
+  float *d_tiles = nullptr, *d_rgb = nullptr;
+  uint32_t *d_gt = nullptr, *d_gs = nullptr;
+  int rc = RT_OK;
+  if (hipMalloc((void**)&d_tiles, nt * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&d_rgb, npx * 3 * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&d_gt, ng * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc((void**)&d_gs, nsw * sizeof(uint32_t)) != hipSuccess)
+    rc = rt_set_error(RT_EHIP, "hipMalloc image and G-buffer");
+  const int was = c->gbuffer;
+  c->gbuffer = 1;
+  rt_stats tmp;
+  const bool have = rc == RT_OK;
+  for (int attempt = 0; have && attempt < 3; attempt++) {  // again after the hit or list buffers grew
+    rc = rt_hip_render(c, f, 0, 1, d_tiles, nullptr);
+    if (!rc) rc = rt_hip_assemble(c, f, d_tiles, 1, d_rgb, nullptr);
+    if (!rc) rc = rt_hip_gbuffer(c, f, 0, 1, d_gt, nullptr);
+    if (!rc) rc = rt_hip_assemble_gbuffer(c, f, d_gt, 1, d_gs, nullptr);
+    if (!rc && (hipMemcpyAsync(h_rgb, d_rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream) !=
+                    hipSuccess ||
+                hipMemcpyAsync(h_samples, d_gs, nsw * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream) !=
+                    hipSuccess))
+      rc = rt_set_error(RT_EHIP, "D2H image and G-buffer");
+    if (!rc) rc = rt_hip_stats(c, st ? st : &tmp);
+    if (rc != RT_EHITBUF) break;
+  }
+  c->gbuffer = was;
+  if (!was) c->gb_valid = 0;
+  (void)hipFree(d_tiles);
+  (void)hipFree(d_rgb);
+  (void)hipFree(d_gt);
+  (void)hipFree(d_gs);
   return rc;
 }
 

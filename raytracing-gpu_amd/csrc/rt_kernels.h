@@ -80,7 +80,14 @@
 // the default policy): the default plus reflection rays through the proven
 // walk (csrc/rt_reflect.hip: per-node error-region growth)
 #define RT_POLICY_EXACT_REFL 5
-#define RT_NPOLICIES 6
+// trace kernel only, chosen by the host (rt_hip_set_gbuffer with the default
+// policy, octree or FLAT): the default plus one capture record per camera
+// sample (KParams::capture) -- the default kernel has no register to spare
+// for it, so it has no switch either
+#define RT_POLICY_GBUFFER 6
+#define RT_NPOLICIES 7
+// words of one public G-buffer sample record (include/rt_hip.h rt_gsample)
+#define RT_GB_WORDS_D 10
 
 // wave-total counters (wave-uniform, so they live in SGPRs; 32-bit per wave,
 // widened to 64-bit by the final atomics)
@@ -183,6 +190,11 @@ struct KParams {
   // or NULL
   unsigned long long* frame_check;
   const uint32_t* list_flag;
+  // G-buffer capture (RT_POLICY_GBUFFER; NULL otherwise), per (item, lane) like
+  // `last`: the camera query's winner prim (~0: none) | bits of its new_dist |
+  // the path's first hit record (RT_NO_REC: none) | the path's closest-hit
+  // queries.  The last member: every other kernel's argument offsets stay put
+  uint4* capture;
 };
 #define RT_FRAME_HITBUF 1u     // hit records past a region's capacity
 #define RT_FRAME_DEPTH 2u      // bounce limit or traversal stack overflow
@@ -223,3 +235,11 @@ extern "C" hipError_t rt_launch_downscale(const uint32_t* hi, uint32_t* lo, int 
 extern "C" hipError_t rt_launch_assemble(const float* tiles, float* rgb, int W, int H, int tiles_x,
                                          int ntiles, int nranks, int tiles_per_rank,
                                          hipStream_t stream);
+// G-buffer of the last render with p->capture set (its KParams): the rank's
+// tile buffer of 4 * RT_GB_WORDS_D words per pixel slot, one thread per
+// (pixel, sample)
+extern "C" hipError_t rt_launch_gbuffer(const KParams* p, uint32_t* out, hipStream_t stream);
+// rt_launch_assemble for tile buffers of `words` 32-bit words per pixel slot
+extern "C" hipError_t rt_launch_assemble_words(const uint32_t* tiles, uint32_t* out, int W, int H, int tiles_x,
+                                               int nranks, int tiles_per_rank, int words,
+                                               hipStream_t stream);

@@ -1794,15 +1794,27 @@ __device__ __forceinline__ bool camera_sample(const KParams& p, uint32_t t, int 
   return valid;
 }
 
+// A lane's G-buffer capture record (KParams::capture), as initialised: no
+// winner, no record, no query.
+struct Capture {
+  uint32_t prim = 0xffffffffu;
+  uint32_t dist = 0x7f800000u;  // +inf
+  uint32_t first = RT_NO_REC;
+  uint32_t queries = 0;
+};
+
 // One camera sample for every lane of the wave (trace_kernel): the
 // recursion as a wave-uniform bounce loop, a hit record appended per hit (one
 // atomic per wave and bounce, on the item stream's own counter x).  Returns
 // the lane's deepest record (RT_NO_REC: none).  valid = the lane owns a pixel.
+// RT_POLICY_GBUFFER only: cap = the lane's capture record (KParams::capture),
+// filled at the camera query (depth 0), its query count on every bounce.
 template <int ACCEL, bool COUNT, int POL>
 __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 o, f3 d,
                                                uint32_t x, Stack& s, WaveCtx& w, WorkCount& wc,
-                                               uint32_t tile, int depth = 0, float coef = 1.0f,
+                                               uint32_t tile, Capture& cap, int depth = 0, float coef = 1.0f,
                                                uint32_t prev = RT_NO_REC) {
+  constexpr bool kCapture = POL == RT_POLICY_GBUFFER;
   // depth: wave-uniform, queries so far on this path
   bool alive = valid;
   for (;;) {
@@ -1810,6 +1822,7 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     uint64_t am = __ballot(alive);
     if (am == 0) break;
     wc.closest += (uint32_t)__popcll(am);  // wave-uniform counters (SGPRs)
+    if (kCapture && alive) cap.queries++;  // the lane's own share of wc.closest
     Ray r = make_ray(p, o, d, depth == 0 ? p.eps_rel_cam : p.eps_rel);
     Best b;
     b.dist = __builtin_inff();
@@ -1828,6 +1841,10 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     if (ACCEL != RT_ACCEL_FLAT_D && depth == 0) cand_closest<COUNT>(p, r, alive, tile, b, w, wc);
     if (COUNT) wc.cy_cand += (uint32_t)(__builtin_readcyclecounter() - c0);
     bool hit = alive && b.dist != __builtin_inff();
+    if (kCapture && depth == 0 && hit) {  // the camera query's winner, a zero-normal one included
+      cap.prim = b.prim;
+      cap.dist = __float_as_uint(b.dist);
+    }
     f3 N = f3{0.0f, 0.0f, 0.0f};
     wc.hits += (uint32_t)__popcll(__ballot(hit));
     bool zero = false;
@@ -1855,6 +1872,7 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
         p.hit_prev[a] = prev;
       }
       prev = x | (slot << 3);
+      if (kCapture && depth == 0) cap.first = prev;
       const float ncoef = p.mat[RT_MAT_FLOATS_D * (size_t)b.obj + 10] * coef;  // obj.nr * coef
       if (depth + 1 >= RT_MAX_BOUNCES) {
         deep = !((double)ncoef < 0.01);  // cpu/rt would query again: never silent
@@ -1945,8 +1963,11 @@ __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void trace_kernel(KParams p
     f3 point, dir;
     const bool valid = camera_sample(p, t, smp, lane, point, dir);
     if (smp == 0) wc.pixels += (uint32_t)__popcll(__ballot(valid));
+    Capture cap;
     p.last[(size_t)u * 64 + lane] =
-        trace_path<ACCEL, COUNT, POL>(p, valid, point, dir, x, stk, w, wc, t, 0, 1.0f, RT_NO_REC);
+        trace_path<ACCEL, COUNT, POL>(p, valid, point, dir, x, stk, w, wc, t, cap, 0, 1.0f, RT_NO_REC);
+    if (POL == RT_POLICY_GBUFFER)  // one 16-byte vector store per lane
+      p.capture[(size_t)u * 64 + lane] = make_uint4(cap.prim, cap.dist, cap.first, cap.queries);
     if (prio) __builtin_amdgcn_s_setprio(0);
     if (p.item_cost && lane == 0) {  // the next frame's work order (rt_cand_order)
       const unsigned long long cy = __builtin_readcyclecounter() - c0;
@@ -2583,6 +2604,68 @@ __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__
   (void)ntiles;
 }
 
+// The same map for tile buffers of `words` 32-bit words per pixel slot (the
+// G-buffer's 4 * RT_GB_WORDS_D): one thread per output word.
+__global__ __launch_bounds__(256) void assemble_words_kernel(const uint32_t* __restrict__ tiles,
+                                                             uint32_t* __restrict__ out, int W, int H,
+                                                             int tiles_x, int nranks, int tiles_per_rank,
+                                                             int words) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)W * (size_t)H * (size_t)words) return;
+  const size_t px = idx / (size_t)words;
+  const int k = (int)(idx % (size_t)words);
+  const int row = (int)(px / (size_t)W), col = (int)(px % (size_t)W);
+  uint32_t rank;
+  const int tb = rt_block_side(nranks);
+  const uint32_t local = rt_tile_local(col >> 3, row >> 3, (uint32_t)nranks,
+                                       (uint32_t)rt_blocks_x(tiles_x, tb), (uint32_t)tb, &rank);
+  const int lane = ((row & 7) << 3) | (col & 7);
+  out[idx] = tiles[(((size_t)rank * tiles_per_rank + local) * 64 + lane) * (size_t)words + k];
+}
+
+// The G-buffer of a render traced with RT_POLICY_GBUFFER (p = its KParams):
+// one thread per (pixel slot, sample) of the rank's tiles turns the sample's
+// capture record and its path's first hit record into the public record
+// (include/rt_hip.h rt_gsample: prim obj queries dist P N) at words
+// [RT_GB_WORDS_D * (4 * slot + sample), ...) of `out` -- consecutive threads
+// write consecutive records, five 8-byte stores each.  Padding slots and
+// pixels outside the framebuffer's even-sized area (fold_kernel's test) are
+// misses without a query.
+__global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __restrict__ out) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)p.ntiles_local * 256u) return;
+  const uint32_t slot = (uint32_t)(g >> 2), smp = (uint32_t)g & 3u;
+  const uint32_t t = slot >> 6, lane = slot & 63u;
+  int pr, pc;
+  tile_pixel(p, t, (int)lane, pr, pc);
+  const int ii = p.W - pc, jj = p.H - pr;
+  const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 &&
+                     jj <= 2 * (p.H / 2);
+  uint32_t prim = 0xffffffffu, obj = 0xffffffffu, queries = 0, dist = 0x7f800000u;
+  float4 h0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), h1 = h0;
+  if (valid) {
+    const uint4 c = p.capture[((size_t)t * 4 + smp) * 64 + lane];
+    queries = c.w;
+    if (c.x != 0xffffffffu) {
+      prim = c.x;
+      dist = c.y;
+      obj = __float_as_uint(p.tri_prim[3 * (size_t)prim + 2].z);
+      // no record: a zero-normal winner, or one past the buffer (RT_EHITBUF)
+      if (c.z != RT_NO_REC && (c.z >> 3) < p.hit_cap) {
+        const size_t a = rec_addr(p, c.z);
+        h0 = p.hit[2 * a];
+        h1 = p.hit[2 * a + 1];
+      }
+    }
+  }
+  uint2* o = (uint2*)(out + g * RT_GB_WORDS_D);
+  o[0] = make_uint2(prim, obj);
+  o[1] = make_uint2(queries, dist);
+  o[2] = make_uint2(__float_as_uint(h0.x), __float_as_uint(h0.y));
+  o[3] = make_uint2(__float_as_uint(h0.z), __float_as_uint(h0.w));
+  o[4] = make_uint2(__float_as_uint(h1.x), __float_as_uint(h1.y));
+}
+
 }  // namespace rt
 
 // ---------------------------------------------------------------- launchers
@@ -2599,6 +2682,10 @@ static const void* kernel_of(int accel, int count_work, int policy);
 template <bool TRACE>
 static const void* kernel_of(int accel, int count_work, int policy) {
   using namespace rt;
+  // the capturing trace (no counting variant: the host refuses the pair)
+  if (TRACE && policy == RT_POLICY_GBUFFER)
+    return accel == RT_ACCEL_FLAT_D ? (const void*)trace_kernel<RT_ACCEL_FLAT_D, false, RT_POLICY_GBUFFER>
+                                    : (const void*)trace_kernel<RT_ACCEL_OCTREE_D, false, RT_POLICY_GBUFFER>;
   if (accel == RT_ACCEL_FLAT_D) {
     if (TRACE)
       return count_work ? (const void*)trace_kernel<RT_ACCEL_FLAT_D, true, 0>
@@ -2699,6 +2786,24 @@ extern "C" hipError_t rt_launch_assemble(const float* tiles, float* rgb, int W, 
   dim3 g((unsigned)((npx + 255) / 256)), b(256);
   hipLaunchKernelGGL(rt::assemble_kernel, g, b, 0, stream, tiles, rgb, W, H, tiles_x, ntiles,
                      nranks, tiles_per_rank);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_gbuffer(const KParams* p, uint32_t* out, hipStream_t stream) {
+  const size_t n = (size_t)p->ntiles_local * 256u;
+  if (n == 0) return hipGetLastError();
+  hipLaunchKernelGGL(rt::gbuffer_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *p, out);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_assemble_words(const uint32_t* tiles, uint32_t* out, int W, int H, int tiles_x,
+                                               int nranks, int tiles_per_rank, int words,
+                                               hipStream_t stream) {
+  const size_t n = (size_t)W * (size_t)H * (size_t)words;
+  if (n == 0) return hipGetLastError();
+  if ((n + 255) / 256 > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rt::assemble_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, tiles,
+                     out, W, H, tiles_x, nranks, tiles_per_rank, words);
   return hipGetLastError();
 }
 

@@ -200,6 +200,13 @@ _PROTOS = [
                                       C.c_uint, C.c_void_p]),
     ("rt_hip_render_image", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p,
                                       C.POINTER(Stats)]),
+    ("rt_hip_set_gbuffer", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_hip_gbuffer_tile_words", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("rt_hip_gbuffer", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("rt_hip_assemble_gbuffer", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
+    ("rt_hip_render_image_gbuffer", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats)]),
     ("rt_hip_malloc", C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("rt_hip_free", C.c_int, [C.c_void_p]),
     ("rt_hip_memcpy_d2h", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -437,6 +444,41 @@ def tile_buffer_floats(width, height, nranks):
     return int(lib().rt_hip_tile_buffer_floats(width, height, nranks))
 
 
+# ---- per-sample G-buffer (include/rt_hip.h rt_gsample) ----
+GB_WORDS = 10
+GSAMPLE = np.dtype([("prim", np.int32), ("obj", np.int32), ("queries", np.int32), ("dist", np.float32),
+                    ("P", np.float32, 3), ("N", np.float32, 3)])
+assert GSAMPLE.itemsize == 4 * GB_WORDS
+
+
+def gbuffer_tile_words(width, height, nranks):
+    """32-bit words of one rank's G-buffer tile buffer (rt_hip_gbuffer_tile_words)."""
+    return int(lib().rt_hip_gbuffer_tile_words(width, height, nranks))
+
+
+def prim_object_triangle(scene, prim):
+    """(object index, index into that object's triangle array) of the global
+    triangle index `prim` of a G-buffer sample (objects in file order, each
+    object's triangles in array order); prim = -1 (miss) gives (-1, -1)."""
+    prim = int(prim)
+    if prim < 0:
+        return -1, -1
+    s = _as_scene_ptr(scene.ptr if isinstance(scene, Scene) else scene).contents
+    base = 0
+    for i in range(s.object_count):
+        n = int(s.objects[i].triangle_count)
+        if prim < base + n:
+            return i, prim - base
+        base += n
+    raise IndexError(f"prim {prim} of {base} triangles")
+
+
+def coverage(samples):
+    """(H, W) float32 alpha in {0, 1/4, 1/2, 3/4, 1}: the share of each pixel's
+    four samples whose camera ray hit geometry."""
+    return ((samples["prim"] >= 0).sum(axis=-1) * 0.25).astype(np.float32)
+
+
 class Context:
     """One device image of a scene (rt_hip_create); renders through the C ABI."""
 
@@ -669,6 +711,35 @@ class Context:
                            "rt_hip_render_image")
         return img, st.as_dict()
 
+    def set_gbuffer(self, on=True):
+        """Renders capture the per-sample G-buffer (rt_hip_set_gbuffer); read
+        it with gbuffer() after each render."""
+        _check(lib().rt_hip_set_gbuffer(self.h, 1 if on else 0), "rt_hip_set_gbuffer")
+
+    def gbuffer(self, frame, rank, nranks, d_tiles, stream=None):
+        """The last render's G-buffer tile buffer (rt_hip_gbuffer): d_tiles =
+        device memory of gbuffer_tile_words() words."""
+        _check(lib().rt_hip_gbuffer(self.h, C.byref(frame), rank, nranks, C.c_void_p(d_tiles),
+                                    C.c_void_p(stream) if stream else None), "rt_hip_gbuffer")
+
+    def assemble_gbuffer(self, frame, d_gathered, nranks, d_samples, stream=None):
+        """Gathered G-buffer tile buffers -> H*W*4 records in PPM order."""
+        _check(lib().rt_hip_assemble_gbuffer(self.h, C.byref(frame), C.c_void_p(d_gathered), nranks,
+                                             C.c_void_p(d_samples), C.c_void_p(stream) if stream else None),
+               "rt_hip_assemble_gbuffer")
+
+    def render_image_gbuffer(self, frame):
+        """Whole frame on this device -> (H, W, 3) float32 image, (H, W, 4)
+        GSAMPLE records (a pixel's four samples in cpu order), stats."""
+        img = np.empty((frame.height, frame.width, 3), np.float32)
+        smp = np.empty((frame.height, frame.width, 4), GSAMPLE)
+        st = Stats()
+        self._check_render(lib().rt_hip_render_image_gbuffer(self.h, C.byref(frame),
+                                                             img.ctypes.data_as(C.c_void_p),
+                                                             smp.ctypes.data_as(C.c_void_p), C.byref(st)),
+                           "rt_hip_render_image_gbuffer")
+        return img, smp, st.as_dict()
+
     def render_compat(self, camera):
         """gpu/rt compatibility mode (rt_hip_render_compat) -> (H, W, 4)
         uint8 RGBA in gpu/rt's PNG row order, stats."""
@@ -842,6 +913,19 @@ def assemble_tiles_numpy(gathered, width, height, nranks):
     tiling / gather layout): gathered = nranks x tiles_per_rank x 64 x 3."""
     tpr = tiles_per_rank_host(width, height, nranks)
     g = np.asarray(gathered, np.float32).reshape(nranks, tpr, 64, 3)
+    rows, cols = np.mgrid[0:height, 0:width]
+    rk, loc = tile_local(cols // 8, rows // 8, nranks, width, height)
+    lane = (rows % 8) * 8 + (cols % 8)
+    return g[rk, loc, lane]
+
+
+def assemble_gbuffer_numpy(gathered, width, height, nranks, words=4 * GB_WORDS):
+    """assemble_tiles_numpy for tile buffers of `words` 32-bit words per pixel
+    slot (the assemble_words kernel's index map): gathered = nranks x
+    tiles_per_rank x 64 x words of any 4-byte dtype -> (H, W, words) uint32;
+    view the G-buffer's 40 words as GSAMPLE for (H, W, 4) records."""
+    tpr = tiles_per_rank_host(width, height, nranks)
+    g = np.ascontiguousarray(gathered).view(np.uint32).reshape(nranks, tpr, 64, words)
     rows, cols = np.mgrid[0:height, 0:width]
     rk, loc = tile_local(cols // 8, rows // 8, nranks, width, height)
     lane = (rows % 8) * 8 + (cols % 8)
