@@ -113,12 +113,11 @@ extern "C" int rt_cand_verify_host(const CandParams* p, const float* tri, const 
 extern "C" hipError_t rt_cand_prim_leaf(const float4* node, uint32_t nnode, const float4* tri,
                                         uint32_t* prim_leaf, hipStream_t s);
 
-// pass 0 (float fast path flags) -> scan -> scatter (compact list of the
-// rest) -> pass 1 (their footprints and tile counts) -> exclusive scan ->
-// pass 2 ((tile, prim) pairs at the offsets) -> radix sort by tile ->
-// per-tile offsets
+// pass 0 (float fast path flags) -> scan + scatter (rt_cand_scan_scatter: the
+// compact list of the rest) -> pass 1 (their footprints and tile counts) ->
+// exclusive scan -> pass 2 ((tile, prim) pairs at the offsets) -> radix sort
+// by tile -> per-tile offsets
 extern "C" hipError_t rt_cand_quick(const CandParams* p, hipStream_t s);
-extern "C" hipError_t rt_cand_scatter(const CandParams* p, hipStream_t s);
 extern "C" hipError_t rt_cand_count(const CandParams* p, hipStream_t s);
 extern "C" size_t rt_cand_footprint_bytes(void);
 // pass 1b: tile counts of the big footprints (one wave each)

@@ -247,10 +247,6 @@ RTC_FN int classify(const CandParams& p, const float* r, const float* leafbox, F
   const double rT = pt_tri_dist(p.pos, v0, v1, v2);
   if (!(rT > 2.0 * p.dline + 1e-9)) return GLOBAL;
   const double c_band = fmin(1.0, (deye + p.dline + kmax_ch) / (rT - p.dline));
-#ifndef RT_CAND_CMIN
-#define RT_CAND_CMIN 1
-#endif
-#if RT_CAND_CMIN
   // cpu/hit.c:19-20 rejects |a| < 1e-7, and |a| <= kDMax nl c + e_a: no
   // line with c < c_min is accepted.  Every candidate line has c <= c_band,
   // so c_min > c_band leaves none (with c_ok > 0 the lines below c_ok are
@@ -259,13 +255,6 @@ RTC_FN int classify(const CandParams& p, const float* r, const float* leafbox, F
     if (why) *why = 3;
     return SAFE;
   }
-#endif
-#if defined(RT_SURVEY_DUMP) && !defined(__HIP_DEVICE_COMPILE__)
-  if (td) {
-    td[7] = nl; td[8] = deye; td[9] = rT; td[10] = c_band; td[11] = (kAMin - e_a) / (kDMax * nl);
-    td[12] = cl; td[13] = hreach; td[14] = kmax_ch; td[15] = e_a; td[16] = e_sh; td[17] = a_lb;
-  }
-#endif
   const double wide = p.lmax + p.dline + p.dorig;
   fp.b0 = dot3(nh, p.pos) - dot3(nh, p.C);
   fp.b1 = -dot3(nh, p.u);
@@ -410,10 +399,6 @@ RTC_FN bool rank_may_touch(const CandParams& p, const double q[3], double rb) {
 
 enum { Q_SAFE = 0, Q_LIST = 1, Q_AWAY = 2 };
 
-#ifndef RT_QUICK_TIGHT
-#define RT_QUICK_TIGHT 1
-#endif
-
 // Fast, conservative float version of classify()'s SAFE test (no leaf box):
 // every quantity is a positive magnitude computed in a few float operations,
 // bounded with explicit margins, so a true result is a proof on its own.
@@ -535,7 +520,10 @@ RTC_FN int quick_class(const CandParams& p, const float* r, float* dbg = nullptr
       h = H(cl, a, rho);
     }
   }
-  if (RT_QUICK_TIGHT) h = Ht(cl, a, rho);
+  // the final reach from the corners' own displacements (the common bound
+  // H alone measured lists 2.18 / 2.20 vs 1.97 / 1.96 ms on C5,
+  // profiles/r08_quick_tight/, removed)
+  h = Ht(cl, a, rho);
   const float rmax = vmax + h;
   const float derr = (e_eq / (a * (1.0f - rho)) + (rmax + (float)p.lmax) * (rho + 4.0f * fe) / (1.0f - rho) +
                       4.0f * fe * ((float)p.omax + rmax + (float)p.lmax)) * 1.0001f;
@@ -944,20 +932,19 @@ constexpr int kBigWaves = 4096;
 #ifndef RT_LIST_BLOCK
 #define RT_LIST_BLOCK 256
 #endif
-// bits per radix place of the lists' sort (0: rocPRIM's tuned default, 8):
+// bits per radix place of the lists' sort (rocPRIM's tuned default is 8):
 // 9 sorts C5's 17-bit tile keys in two places instead of three (lists 2.13
 // -> 1.98 ms; 6 bits: 2.20; profiles/r04o_sort_bits/)
-#ifndef RT_SORT_BITS
-#define RT_SORT_BITS 9
-#endif
+static constexpr unsigned kSortBits = 9;
 #ifndef RT_SORT_MERGE_LIMIT
 #define RT_SORT_MERGE_LIMIT (1u << 16)
 #endif
 
 // Pass 0: the float fast path over every prim; flags the prims it cannot
-// prove safe (visits[prim] = 1), which an exclusive scan and scatter_kernel
-// turn into a compact list, so the f64 classification of pass 1 runs on full
-// waves instead of on the scattered third of the lanes of every wave.
+// prove safe (visits[prim] = 1), which the fused scan and scatter of
+// rt_cand_scan_scatter turn into a compact list, so the f64 classification
+// of pass 1 runs on full waves instead of on the scattered third of the lanes
+// of every wave.
 // the i-th prim of the build's slice (CandParams::prim0, sl_stride)
 __device__ __forceinline__ uint32_t slice_prim(const CandParams& p, uint32_t i) {
   if (p.sl_stride <= 1u) return p.prim0 + i;
@@ -976,17 +963,6 @@ __global__ __launch_bounds__(RT_LIST_BLOCK, RT_QUICK_WAVES) void quick_kernel(Ca
   if (i == 0u) p.visits[len] = 0u;    // the scan's last input
   if (i >= len) return;
   p.visits[i] = quick_class(p, (const float*)(p.tri + 3 * (size_t)slice_prim(p, i))) == Q_LIST ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(256) void scatter_kernel(CandParams p) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t len = p.prim1 - p.prim0;
-  if (i > len) return;
-  if (i == len) {
-    p.ctr[3] = p.off[len];  // list length
-    return;
-  }
-  if (p.visits[i]) p.list[p.off[i]] = slice_prim(p, i);
 }
 
 // The footprints whose entries are refined per tile (CandParams::refine):
@@ -1037,11 +1013,9 @@ __device__ __forceinline__ bool small_pack(const CandParams& p, const Footprint&
   return n <= kSmallEntries;
 }
 
-// the classification's leaf box loaded at its start instead of at its use
-// (A/B knob: lists 1.803 -> 1.816 ms at 128 VGPRs, profiles/r08_list_occupancy/)
-#ifndef RT_COUNT_LEAF_AHEAD
-#define RT_COUNT_LEAF_AHEAD 0
-#endif
+// (The classification's leaf box loaded at its start instead of at its use
+// measured lists 1.803 -> 1.816 ms at 128 VGPRs, profiles/r08_list_occupancy/,
+// removed.)
 // Pass 1: classify the listed prims, keep each one's footprint and count the
 // tiles of the small ones (visits[j] for list entry j; visits is zero beyond
 // the list); big ones are queued for big_count_kernel.
@@ -1050,23 +1024,7 @@ __device__ __forceinline__ void count_one(const CandParams& p, uint32_t j) {
   const float* rec = (const float*)(p.tri + 3 * (size_t)prim);
   uint32_t visits = 0;
   Footprint fp;
-#if RT_COUNT_LEAF_AHEAD
-  // the leaf box in registers from the start: its loads (prim -> leaf ->
-  // box, a dependent pair) overlap the f64 bound instead of waiting at its end
-  // (no leaf map: an empty box, which no corner lies in -- the same verdicts
-  // as no box; one array either way keeps it in registers)
-  float4 b0 = make_float4(__builtin_inff(), __builtin_inff(), __builtin_inff(), 0.0f);
-  float4 b1 = make_float4(-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), 0.0f);
-  if (p.prim_leaf) {
-    const float4* nb = p.node + 2 * (size_t)p.prim_leaf[prim];
-    b0 = nb[0];
-    b1 = nb[1];
-  }
-  const float lbox[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-  const float* lb = lbox;
-#else
   const float* lb = p.prim_leaf ? (const float*)(p.node + 2 * (size_t)p.prim_leaf[prim]) : nullptr;
-#endif
   const int c = classify(p, rec, lb, fp);
   if (c == GLOBAL) {
     p.global[atomicAdd(p.ctr + 1, 1u)] = prim;
@@ -1899,9 +1857,6 @@ extern "C" int rt_cand_survey_host(const CandParams* p, const float* tri, const 
   std::vector<unsigned long long> part(88 * (size_t)threads, 0);
   std::vector<unsigned long long> bad((size_t)threads, 0);
   std::vector<std::thread> th;
-#ifdef RT_SURVEY_DUMP
-  std::vector<std::vector<double>> dump((size_t)threads);
-#endif
   for (int t = 0; t < threads; t++)
     th.emplace_back([&, t]() {
       unsigned long long* o = &part[88 * (size_t)t];
@@ -1965,22 +1920,7 @@ extern "C" int rt_cand_survey_host(const CandParams* p, const float* tri, const 
               rtc::row_ivs(*p, fp, ty, q0, q1, x, fb, cn);
               vi += cn[0] + cn[1] + cn[2];
             }
-          if (v != rtc::raster_count(*p, fp) || vi != v) {
-            bad[t]++;  // the device count pass must agree
-#ifdef RT_SURVEY_DEBUG
-            int r0, r1;
-            rtc::raster_rows(*p, fp, r0, r1);
-            for (int ty = r0 >> 3; ty <= (r1 >> 3); ty++) {
-              unsigned long long vr = 0;
-              rtc::raster_row(*p, fp, ty, r0, r1, [&](uint32_t) { vr++; });
-              int a0, a1, b0, b1;
-              rtc::row_tiles(*p, fp, ty, r0, r1, a0, a1, b0, b1);
-              if (vr != rtc::count_row(*p, fp, ty, r0, r1))
-                fprintf(stderr, "prim %u ty %d iter %llu count %u a %d..%d b %d..%d\n", i, ty, vr,
-                        rtc::count_row(*p, fp, ty, r0, r1), a0, a1, b0, b1);
-            }
-#endif
-          }
+          if (v != rtc::raster_count(*p, fp) || vi != v) bad[t]++;  // the device count pass must agree
           o[3] += v;
           if (!v && qc == rtc::Q_LIST) o[74]++;
           int k = 0;
@@ -2002,22 +1942,10 @@ extern "C" int rt_cand_survey_host(const CandParams* p, const float* tri, const 
           while (kg < 15 && g >= p->eps_avail * std::ldexp(1.0, kg - 7)) kg++;
           o[36 + kg]++;
           o[52 + kg] += v;
-#ifdef RT_SURVEY_DUMP
-          dump[t].push_back((double)i);
-          dump[t].push_back((double)v);
-          for (int q = 7; q < 18; q++) dump[t].push_back(td[q]);
-#endif
         }
       }
     });
   for (auto& x : th) x.join();
-#ifdef RT_SURVEY_DUMP
-  if (const char* fn = getenv("RT_SURVEY_DUMP_FILE")) {
-    FILE* fo = fopen(fn, "wb");
-    for (auto& d : dump) fwrite(d.data(), sizeof(double), d.size(), fo);
-    fclose(fo);
-  }
-#endif
   for (int k = 0; k < 88; k++) {
     out[k] = 0;
     for (int t = 0; t < threads; t++) out[k] += part[88 * (size_t)t + k];
@@ -2188,12 +2116,6 @@ extern "C" hipError_t rt_cand_quick(const CandParams* p, hipStream_t s) {
   return hipGetLastError();
 }
 
-extern "C" hipError_t rt_cand_scatter(const CandParams* p, hipStream_t s) {
-  const uint32_t len = p->prim1 - p->prim0;
-  hipLaunchKernelGGL(rtc::scatter_kernel, dim3((len + 1 + 255) / 256), dim3(256), 0, s, *p);
-  return hipGetLastError();
-}
-
 extern "C" hipError_t rt_cand_count(const CandParams* p, hipStream_t s) {
   const uint32_t len = p->prim1 - p->prim0;  // the list holds prims of the slice only
   if (len == 0) return hipSuccess;
@@ -2300,8 +2222,7 @@ extern "C" hipError_t rt_cand_scan(const uint32_t* in, uint32_t* out, uint32_t n
 extern "C" hipError_t rt_cand_sort(uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_in,
                                    uint32_t* vals_out, uint32_t n, int begin_bit, int end_bit, void* temp,
                                    size_t* temp_bytes, hipStream_t s) {
-#if RT_SORT_BITS
-  // digits of RT_SORT_BITS bits per onesweep place (rocPRIM's gfx950 u32/u32
+  // digits of kSortBits bits per onesweep place (rocPRIM's gfx950 u32/u32
   // tuning otherwise: 8 bits, so C5's 17-bit tile keys take three places)
   // onesweep from RT_SORT_MERGE_LIMIT items up (rocPRIM's default switches
   // at 2^20: a consume of ~1 M entries at N = 8 went through 9 merge passes,
@@ -2309,14 +2230,10 @@ extern "C" hipError_t rt_cand_sort(uint32_t* keys_in, uint32_t* keys_out, uint32
   using cfg = rocprim::radix_sort_config<
       rocprim::default_config, rocprim::default_config,
       rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 16>, rocprim::kernel_config<1024, 16>,
-                                          RT_SORT_BITS, rocprim::block_radix_rank_algorithm::match>,
+                                          rtc::kSortBits, rocprim::block_radix_rank_algorithm::match>,
       RT_SORT_MERGE_LIMIT>;
   return rocprim::radix_sort_pairs<cfg>(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n,
                                         begin_bit, end_bit, s);
-#else
-  return rocprim::radix_sort_pairs(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out,
-                                   (size_t)n, begin_bit, end_bit, s);
-#endif
 }
 
 extern "C" hipError_t rt_cand_entry_skip(const uint32_t* cand, const float* skip, float* out,

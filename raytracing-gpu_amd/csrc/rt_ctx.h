@@ -58,27 +58,6 @@ extern "C" {
 
 #define RT_TIMED_FRAMES 1024
 
-// the trace's work order puts the long items of the same frame's previous
-// trace first (rt_cand.hip heavy_flag_kernel); 0: entries only (A/B knob)
-// asynchronous list builds compact the refinement's kept entries before the
-// sort (rt_cand_compact); 0: sort them all (A/B knob)
-#ifndef RT_COMPACT_LISTS
-#define RT_COMPACT_LISTS 1
-#endif
-// asynchronous list builds for a new camera of the same size and rank split,
-// sized from the last build + headroom (cand_prepare; A/B knob)
-#ifndef RT_ASYNC_NEW_CAMERA
-#define RT_ASYNC_NEW_CAMERA 1
-#endif
-// ... also in a fresh (non-asynchronous) build, with a read-back of the kept
-// count (A/B knob)
-#ifndef RT_COMPACT_FRESH
-#define RT_COMPACT_FRESH 1
-#endif
-#ifndef RT_COST_ORDER
-#define RT_COST_ORDER 1
-#endif
-
 // per-frame counters (one allocation, rt_hip_ctx::d_counter): 8 item-stream
 // counters 128 B apart, the stats, RT_HIT_REGIONS hit-record and as many
 // shade-chunk counters 32 words apart
@@ -288,6 +267,35 @@ static inline void lists_changed(rt_hip_ctx* c) {
   c->kept_pending = c->snap_pending = 0;
 }
 
+// The unit of the culling slacks: eps_ulps of them, relative to the
+// origin-to-geometry distance (2^-24; DESIGN.md "Conservative culling").
+static constexpr float kSlackUnit = 5.9604645e-8f;
+
+// Kernel parameters with the context's scene filled in and everything else
+// zero: what every launch that takes a KParams starts from (the renders, the
+// probes of rt_verify.cpp).
+static inline KParams scene_params(const rt_hip_ctx* c) {
+  KParams p;
+  std::memset(&p, 0, sizeof p);
+  p.tri = c->d_tri;
+  p.nrm = c->d_nrm;
+  p.mat = c->d_mat;
+  p.light = c->d_light;
+  p.node = c->d_node;
+  p.nrec = c->nrec;
+  p.nlight = c->nlight;
+  // prim-order records: camera candidates, light buffers and the exact
+  // shadow mode's global list all index them (set with or without lists)
+  p.tri_prim = c->d_tri_prim;
+  p.spill = c->d_spill;
+  p.scene_c = rt::f3{c->scene_c[0], c->scene_c[1], c->scene_c[2]};
+  p.scene_r = c->scene_r;
+  p.scene_cmag = std::fmax(std::fabs(c->scene_c[0]), std::fmax(std::fabs(c->scene_c[1]),
+                                                               std::fabs(c->scene_c[2])));
+  p.eps_rel = c->eps_ulps * kSlackUnit;
+  p.eps_rel_cam = c->cam_eps_ulps * kSlackUnit;  // camera rays (bounce depth 0)
+  return p;
+}
 
 int cand_params(const rt_frame* f, const float scene_c[3], float scene_r, float eps_ulps, double bound_scale,
                 int rank, int nranks, CandParams* out, int compat = 0);

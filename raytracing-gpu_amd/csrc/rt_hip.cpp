@@ -128,7 +128,7 @@ int shadow_prepare(rt_hip_ctx* c, hipStream_t s) {
   sp.R = c->scene_r;
   // the walk computes eps(o) in float (host/rt_cull.h); the multipliers keep
   // a relative margin of 1e-6 and the +1 of the original slack on top
-  sp.eps_rel = (double)(c->eps_ulps * 5.9604645e-8f);
+  sp.eps_rel = (double)(c->eps_ulps * kSlackUnit);
   const double cmag = std::fmax(std::fabs(c->scene_c[0]), std::fmax(std::fabs(c->scene_c[1]),
                                                                   std::fabs(c->scene_c[2])));
   sp.plane_eps = (double)RT_CULL_PLANE * (cmag + c->scene_r) + 1e-6;
@@ -181,7 +181,7 @@ void lb_fill(LBParams& lp, const float scene_c[3], float scene_r, const float aa
   std::memset(&lp, 0, sizeof lp);
   // a shadow ray leaves a hit point: inside the scene cube up to the float
   // error of the hit, so its slack eps(o) (host/rt_cull.h, float) is at most
-  const double R = scene_r, eps_rel = (double)(eps_ulps * 5.9604645e-8f);
+  const double R = scene_r, eps_rel = (double)(eps_ulps * kSlackUnit);
   const double cmag = std::fmax(std::fabs(scene_c[0]), std::fmax(std::fabs(scene_c[1]), std::fabs(scene_c[2])));
   const double slack = (eps_rel * (2.0 * R * 1.001 + 1e-3) + (double)RT_CULL_PLANE * (cmag + R) + 1e-6) * 1.01;
   double lo[3], hi[3], s1 = 0.0;
@@ -614,8 +614,10 @@ static int hit_buffers(rt_hip_ctx* c, size_t ntiles) {
   return RT_OK;
 }
 
-extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
-                             float* d_tiles, void* stream) {
+// ---- rt_hip_render, step by step (in the order it runs them) ----
+
+// The refusals: nothing of the context has changed when one of them returns.
+static int render_refuse(const rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, const float* d_tiles) {
   if (!c || !f || !d_tiles) return rt_set_error(RT_EINVAL, "null argument");
   if (nranks <= 0 || rank < 0 || rank >= nranks)
     return rt_set_error(RT_EINVAL, "rank %d of %d", rank, nranks);
@@ -633,22 +635,12 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     if (c->count_work) return rt_set_error(RT_EINVAL, "the G-buffer cannot be captured by the work-counting pass");
     if (c->exact_refl) return rt_set_error(RT_EINVAL, "the G-buffer cannot be captured with exact reflections on");
   }
-  c->gb_valid = 0;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  // lists rt_hip_cand_consume built for exactly this frame and rank: used once
-  const bool use_ext = c->ext_ready && c->ext_rank == rank && c->ext_nranks == nranks &&
-                       std::memcmp(&c->ext_frame, f, sizeof *f) == 0;
-  c->ext_ready = 0;
-  KParams p;
-  std::memset(&p, 0, sizeof p);
-  p.tri = c->d_tri;
-  p.nrm = c->d_nrm;
-  p.mat = c->d_mat;
-  p.light = c->d_light;
-  p.node = c->d_node;
-  p.nrec = c->nrec;
-  p.nlight = c->nlight;
+  return RT_OK;
+}
+
+// The frame's camera and this rank's share of its tiles.
+static void render_frame_params(KParams& p, const rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
+                                float* d_tiles) {
   p.u = rt::f3{f->u.x, f->u.y, f->u.z};
   p.v = rt::f3{f->v.x, f->v.y, f->v.z};
   p.C = rt::f3{f->C.x, f->C.y, f->C.z};
@@ -663,41 +655,41 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   p.out = d_tiles;
   p.tile_counter = c->d_counter;
   p.stats = c->d_stats;
-  p.scene_c = rt::f3{c->scene_c[0], c->scene_c[1], c->scene_c[2]};
-  p.scene_r = c->scene_r;
-  p.scene_cmag = std::fmax(std::fabs(c->scene_c[0]), std::fmax(std::fabs(c->scene_c[1]),
-                                                               std::fabs(c->scene_c[2])));
-  p.spill = c->d_spill;
-  // prim-order records: camera candidates, light buffers and the exact
-  // shadow mode's global list all index them (set with or without lists)
-  p.tri_prim = c->d_tri_prim;
-  // culling slack: eps_ulps ulps of the origin-to-geometry distance
-  // (DESIGN.md "Conservative culling")
-  p.eps_rel = c->eps_ulps * 5.9604645e-8f;
-  p.eps_rel_cam = c->cam_eps_ulps * 5.9604645e-8f;
-  if (p.ntiles_local == 0) {
-    // a rank past the frame's last block (e.g. 96x54 over 8 ranks: 6 blocks)
-    // renders nothing; its tile buffer (sized by rank 0) stays as it is and
-    // gathers as padding.  Its stats read 0.
-    c->cand_prims = c->cand_entries = c->cand_global = 0;
-    c->d_cand_valid = nullptr;
-    c->last_async = 0;
-    hipEvent_t* ev = c->ev[c->frames % RT_TIMED_FRAMES];
-    if (c->timing) HIP_TRY(hipEventRecord(ev[0], s));
-    HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s));
-    c->cost_hist.valid = 0;  // (the counters hold no trace's clocks now)
-    if (c->timing) {
-      for (int k = 1; k < 5; k++) HIP_TRY(hipEventRecord(ev[k], s));
-      c->frames++;
-    }
-    c->last_p = p;
-    c->last_stream = s;
-    if (c->gbuffer) {  // rt_hip_gbuffer of this rank writes nothing either
-      c->gb_frame = *f;
-      c->gb_valid = 1;
-    }
-    return RT_OK;
+}
+
+// The frame's bookkeeping, shared by the empty rank and the full render: the
+// remaining timing events ev[first_ev .. 4], and what rt_hip_stats,
+// rt_hip_verify_shadows and rt_hip_gbuffer read afterwards.
+static int render_done(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hipStream_t s, int first_ev) {
+  c->last_p = p;
+  if (c->gbuffer) {  // (an empty rank's rt_hip_gbuffer writes nothing either)
+    c->gb_frame = *f;
+    c->gb_valid = 1;
   }
+  if (c->timing) {
+    hipEvent_t* ev = c->ev[c->frames % RT_TIMED_FRAMES];
+    for (int k = first_ev; k < 5; k++) HIP_TRY(hipEventRecord(ev[k], s));
+    c->frames++;
+  }
+  c->last_stream = s;
+  return RT_OK;
+}
+
+// A rank past the frame's last block (e.g. 96x54 over 8 ranks: 6 blocks)
+// renders nothing; its tile buffer (sized by rank 0) stays as it is and
+// gathers as padding.  Its stats read 0.
+static int render_nothing(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hipStream_t s) {
+  c->cand_prims = c->cand_entries = c->cand_global = 0;
+  c->d_cand_valid = nullptr;
+  c->last_async = 0;
+  if (c->timing) HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
+  HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s));
+  c->cost_hist.valid = 0;  // (the counters hold no trace's clocks now)
+  return render_done(c, p, f, s, 1);
+}
+
+// The hit-record, capture and (work-counting pass) item-clock buffers.
+static int render_buffers(rt_hip_ctx* c, KParams& p) {
   {
     int rc = hit_buffers(c, (size_t)p.ntiles_local);
     if (rc) return rc;
@@ -722,6 +714,12 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     c->tile_cycles_n = items;
     p.tile_cycles = c->d_tile_cycles;
   }
+  return RT_OK;
+}
+
+// What the shadow queries need: light buffers, the proven walk's multipliers,
+// the off-box queries' queue.
+static int render_shadows(rt_hip_ctx* c, KParams& p, hipStream_t s) {
   {
     // light buffers, proven in exact-shadow mode (no-op unless the slack or
     // the mode changed); the staged policies walk
@@ -755,10 +753,15 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     p.n_sh_global = c->n_sh_global;
     p.sh_omax = c->sh_omax;
   }
+  return RT_OK;
+}
+
+// The camera rays' candidate lists: the ones rt_hip_cand_consume built for
+// this frame (use_ext), or this rank's own build.
+static int render_lists(rt_hip_ctx* c, const rt_frame* f, KParams& p, bool use_ext, hipStream_t s) {
   c->cand_prims = c->cand_entries = c->cand_global = 0;
   c->d_cand_valid = nullptr;
-  hipEvent_t* ev = c->ev[c->frames % RT_TIMED_FRAMES];
-  if (c->timing) HIP_TRY(hipEventRecord(ev[0], s));
+  if (c->timing) HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
   if (c->accel == RT_ACCEL_OCTREE && c->d_node && c->exact_camera) {
     if (use_ext) {  // the lists rt_hip_cand_consume built from the producers' entries
       p.cand_start = c->ext.cand_start;
@@ -779,6 +782,16 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     }
   }
   if (!(c->accel == RT_ACCEL_OCTREE && c->d_node && c->exact_camera && !use_ext)) c->last_async = 0;
+  return RT_OK;
+}
+
+// The kernels a render launches: the device acceleration structure, the
+// trace and shade kernels' policies (their instantiations) and grids.
+struct RenderKernels {
+  int dacc, tpol, spol, gt, gs;
+};
+
+static int render_kernels(rt_hip_ctx* c, KParams& p, hipStream_t s, RenderKernels* out) {
   // an empty octree scene has nothing to traverse: the FLAT kernels with 0
   // records are exact (their grids are the FLAT instantiation's own)
   const bool empty = c->accel == RT_ACCEL_OCTREE && !c->d_node;
@@ -819,6 +832,15 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
     if (items < gt) gt = (int)items;
     if (items < gs) gs = (int)items;
   }
+  *out = RenderKernels{dacc, tpol, spol, gt, gs};
+  return RT_OK;
+}
+
+// The frame's launches: counters zeroed, trace, shade, the deferred shadow
+// queries' fixup, fold.
+static int render_launch(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, KParams& p,
+                         const RenderKernels& k, hipStream_t s) {
+  hipEvent_t* ev = c->ev[c->frames % RT_TIMED_FRAMES];
   // every device pointer the kernels will follow must exist (a null one
   // would fault the card, not fail the call)
   if (!p.tri_prim && (p.lbuf || p.n_sh_global || p.cand_start))
@@ -828,7 +850,7 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   if (c->gbuffer && !p.capture) return rt_set_error(RT_EHIP, "render: G-buffer capture buffer missing");
   // item clocks for the same frame's next work order (only the candidate
   // lists' order uses them)
-  if (p.tile_order && RT_COST_ORDER) {
+  if (p.tile_order) {
     const size_t items = 4 * (size_t)p.ntiles_local;
     if (items > c->item_cost_cap) {
       (void)hipFree(c->d_item_cost);
@@ -849,29 +871,40 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   p.list_flag = c->last_async ? c->d_cand_ctr + 16 + 7 : nullptr;  // bounds_kernel's snapshot of ctr[7]
   HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s));  // item streams, stats, record counters
   if (c->timing) HIP_TRY(hipEventRecord(ev[1], s));
-  HIP_TRY(rt_launch_trace(&p, dacc, c->count_work, tpol, gt, s));
+  HIP_TRY(rt_launch_trace(&p, k.dacc, c->count_work, k.tpol, k.gt, s));
   if (p.item_cost) {
     c->cost_hist.set(f, rank, nranks);
-    c->cost_waves = (uint32_t)gt;
+    c->cost_waves = (uint32_t)k.gt;
   } else {
     c->cost_hist.valid = 0;
   }
   if (c->timing) HIP_TRY(hipEventRecord(ev[2], s));
-  HIP_TRY(rt_launch_shade(&p, dacc, c->count_work, spol, gs, s));
+  HIP_TRY(rt_launch_shade(&p, k.dacc, c->count_work, k.spol, k.gs, s));
   HIP_TRY(rt_launch_shade_fixup(&p, c->nprim, s));
   if (c->timing) HIP_TRY(hipEventRecord(ev[3], s));
   HIP_TRY(rt_launch_fold(&p, s));
-  c->last_p = p;
-  if (c->gbuffer) {
-    c->gb_frame = *f;
-    c->gb_valid = 1;
-  }
-  if (c->timing) {
-    HIP_TRY(hipEventRecord(ev[4], s));
-    c->frames++;
-  }
-  c->last_stream = s;
   return RT_OK;
+}
+
+extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
+                             float* d_tiles, void* stream) {
+  int rc = render_refuse(c, f, rank, nranks, d_tiles);
+  if (rc) return rc;
+  c->gb_valid = 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  // lists rt_hip_cand_consume built for exactly this frame and rank: used once
+  const bool use_ext = c->ext_ready && c->ext_rank == rank && c->ext_nranks == nranks &&
+                       std::memcmp(&c->ext_frame, f, sizeof *f) == 0;
+  c->ext_ready = 0;
+  KParams p = scene_params(c);
+  render_frame_params(p, c, f, rank, nranks, d_tiles);
+  if (p.ntiles_local == 0) return render_nothing(c, p, f, s);
+  RenderKernels k;
+  if ((rc = render_buffers(c, p)) || (rc = render_shadows(c, p, s)) || (rc = render_lists(c, f, p, use_ext, s)) ||
+      (rc = render_kernels(c, p, s, &k)) || (rc = render_launch(c, f, rank, nranks, p, k, s)))
+    return rc;
+  return render_done(c, p, f, s, 4);
 }
 
 extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
@@ -1121,7 +1154,7 @@ extern "C" int rt_hip_render_image_gbuffer(rt_hip_ctx* c, const rt_frame* f, flo
 
 int choose_accel(const rt_scene* s);
 
-// gpu/rt compatibility mode (csrc/rt_render.hip compat_kernel): the frame
+// gpu/rt compatibility mode (csrc/rt_compat.h compat_kernel): the frame
 // of the camera at 3x its size (gpu/rt.cpp:72-83: width and height scaled,
 // so L and C follow), one ray per high-resolution pixel, then the 3x3
 // downscale; h_rgba = width x height RGBA8 in gpu/rt's PNG row order.
@@ -1146,15 +1179,7 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
     return rt_set_error(RT_EHIP, "hipMalloc image");
   }
   hipStream_t s = c->stream;
-  KParams p;
-  std::memset(&p, 0, sizeof p);
-  p.tri = c->d_tri;
-  p.nrm = c->d_nrm;
-  p.mat = c->d_mat;
-  p.light = c->d_light;
-  p.node = c->d_node;
-  p.nrec = c->nrec;
-  p.nlight = c->nlight;
+  KParams p = scene_params(c);
   p.u = rt::f3{f.u.x, f.u.y, f.u.z};
   p.v = rt::f3{f.v.x, f.v.y, f.v.z};
   p.C = rt::f3{f.C.x, f.C.y, f.C.z};
@@ -1168,13 +1193,6 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   p.out = (float*)d_hi;
   p.tile_counter = c->d_counter;
   p.stats = c->d_stats;
-  p.scene_c = rt::f3{c->scene_c[0], c->scene_c[1], c->scene_c[2]};
-  p.scene_r = c->scene_r;
-  p.scene_cmag = std::fmax(std::fabs(c->scene_c[0]), std::fmax(std::fabs(c->scene_c[1]),
-                                                               std::fabs(c->scene_c[2])));
-  p.spill = c->d_spill;
-  p.eps_rel = c->eps_ulps * 5.9604645e-8f;
-  p.eps_rel_cam = c->cam_eps_ulps * 5.9604645e-8f;
   const int accel = (c->accel == RT_ACCEL_FLAT || !c->d_node) ? RT_ACCEL_FLAT_D : RT_ACCEL_OCTREE_D;
   rc = shadow_prepare(c, s);
   if (rc) {
@@ -1188,7 +1206,6 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
     p.n_sh_global = c->n_sh_global;
     p.sh_omax = c->sh_omax;
   }
-  p.tri_prim = c->d_tri_prim;
   // exact camera rays in this mode too: the candidate lists of the 3x frame's
   // one-sample-per-pixel camera (csrc/rt_cand.hip CandParams::compat)
   c->cand_prims = c->cand_entries = c->cand_global = 0;

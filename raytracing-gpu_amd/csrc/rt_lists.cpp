@@ -210,12 +210,9 @@ static constexpr uint32_t kBigLaneCap = 1u << 17;
 #define RT_CAND_ITEM_CAP (1u << 20)
 #endif
 static constexpr uint32_t kItemCap = RT_CAND_ITEM_CAP;
-// the lists' two prim-length scans: the device-length scan of rt_cand.hip
-// (1; the classification's over the listed prims only, no zeroing pass) or
-// rocPRIM's over every prim (0)
-#ifndef RT_DEV_SCAN
-#define RT_DEV_SCAN 1
-#endif
+// (The lists' two prim-length scans are the device-length scan of rt_cand.hip:
+// the classification's over the listed prims only, no zeroing pass.  rocPRIM's
+// scan over every prim with a separate scatter launch was removed.)
 
 extern "C" int rt_hip_set_cand_item_cap(rt_hip_ctx* c, unsigned cap) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
@@ -332,7 +329,7 @@ int cand_params(const rt_frame* f, const float scene_c[3], float scene_r, float 
   const double R = scene_r;
   const double cmag = std::fmax(std::fabs(scene_c[0]), std::fmax(std::fabs(scene_c[1]),
                                                                 std::fabs(scene_c[2])));
-  const double eps_rel = (double)(eps_ulps * 5.9604645e-8f);
+  const double eps_rel = (double)(eps_ulps * kSlackUnit);
   const double eps_min = (eps_rel * (std::fmax(mlb - cp.dorig, 0.0) + R) +
                           (double)RT_CULL_PLANE * (cmag + R) + 1e-6) * (1.0 - 1e-5);
   // the slab test's own rounding (rt_cull.h: a few ulps of |o| and of |t d|)
@@ -553,17 +550,8 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   // pass 0: flags -> compact list of the prims the float fast path leaves
   // (over this build's slice of the prims only)
   if (cp.prim1 > cp.nprim || cp.prim0 > cp.prim1) return rt_set_error(RT_EINVAL, "prim slice");
-  const uint32_t slice = cp.prim1 - cp.prim0;
   HIP_TRY(rt_cand_quick(&cp, s));
-#if RT_DEV_SCAN
-  (void)slice;
   HIP_TRY(rt_cand_scan_scatter(&cp, c->d_scan_bsum, s));
-#else
-  tb = c->scan_tmp_bytes;
-  HIP_TRY(rt_cand_scan(c->d_cand_visits, c->d_cand_off, slice, c->d_scan_tmp, &tb, s));
-  HIP_TRY(rt_cand_scatter(&cp, s));
-  HIP_TRY(hipMemsetAsync(c->d_cand_visits, 0, (np + 1) * sizeof(uint32_t), s));
-#endif
   // pass 1: footprints and tile counts of the listed prims
   HIP_TRY(rt_cand_count(&cp, s));
   HIP_TRY(rt_cand_big_count(&cp, s));
@@ -571,7 +559,6 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   tb = c->scan_tmp_bytes;
   HIP_TRY(rt_cand_scan(c->d_cand_wave_items, c->d_cand_wave_base, rt_cand_big_waves(), c->d_scan_tmp, &tb, s));
   HIP_TRY(rt_cand_items(&cp, s));
-#if RT_DEV_SCAN
   // over the list's length only (ctr[3], on the device); the entry total -> ctr[6]
   HIP_TRY(rt_cand_scan_dev(c->d_cand_visits, c->d_cand_off, (uint32_t)np, c->d_cand_ctr + 3, c->d_cand_ctr + 6,
                            c->d_scan_bsum, s));
@@ -606,12 +593,6 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   // one read-back of the build's sizes: ctr[1..6] (the total in [6], the
   // items in [4])
   HIP_TRY(hipMemcpyAsync(c->h_cand, c->d_cand_ctr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-#else
-  tb = c->scan_tmp_bytes;
-  HIP_TRY(rt_cand_scan(c->d_cand_visits, c->d_cand_off, (uint32_t)np, c->d_scan_tmp, &tb, s));
-  HIP_TRY(hipMemcpyAsync(c->h_cand, c->d_cand_ctr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(c->h_cand + 6, c->d_cand_off + np, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-#endif
   HIP_TRY(hipStreamSynchronize(s));
   const uint32_t total = c->h_cand[6], nglobal = c->h_cand[1], nbig = c->h_cand[2];
   const uint32_t nitems = c->h_cand[4], items_over = c->h_cand[5];
@@ -695,8 +676,8 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   // the compatibility mode and cand_verify's rebuild (every footprint kept)
   // read their sizes back.
   const bool exact_shape = c->known.same(f, kp->rank, kp->nranks);
-  const bool est_shape = !exact_shape && RT_ASYNC_NEW_CAMERA && c->known.same_grid(f, kp->rank, kp->nranks);
-  const bool async = RT_DEV_SCAN && c->async_lists && !c->cand_store_fp && !compat && (exact_shape || est_shape);
+  const bool est_shape = !exact_shape && c->known.same_grid(f, kp->rank, kp->nranks);
+  const bool async = c->async_lists && !c->cand_store_fp && !compat && (exact_shape || est_shape);
   ListShape est = c->known;
   if (est_shape) {
     est.total = c->known.total + c->known.total / 4 + 4096;
@@ -727,15 +708,15 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   // of them on C5): an asynchronous build takes the kept count of the same
   // frame's earlier build; a fresh frame (a new camera: the build read its
   // total back anyway) reads its own back after the compaction's scan -- one
-  // more short host wait instead of sorting the dropped entries
+  // more short host wait instead of sorting the dropped entries (sorting them
+  // all measured lists 1.96 vs 1.83 / 1.85 ms on C5, profiles/r08_compact/)
   // (for a new camera the last frame's kept count + 1/16: the scatter writes
   // the unused tail as dropped, and a count past it sets ctr[7])
   const bool kept_same = c->kept_for.same(f, kp->rank, kp->nranks);
-  const bool compact_known = RT_COMPACT_LISTS && async && c->cand_refine && c->kept_ready &&
-                             (kept_same || (RT_ASYNC_NEW_CAMERA && c->kept_for.same_grid(f, kp->rank, kp->nranks))) &&
+  const bool compact_known = async && c->cand_refine && c->kept_ready &&
+                             (kept_same || c->kept_for.same_grid(f, kp->rank, kp->nranks)) &&
                              c->kept <= total && total > 0;
-  const bool compact_fresh = RT_COMPACT_LISTS && RT_COMPACT_FRESH && !async && !compat && !c->cand_store_fp &&
-                             c->cand_refine && total > 0;
+  const bool compact_fresh = !async && !compat && !c->cand_store_fp && c->cand_refine && total > 0;
   bool kept_now = false;
   if (compact_known || compact_fresh) {
     // the kept entries (stable) -> keys2 / d_cand, sorted back into keys /
@@ -794,7 +775,7 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   // start[nt] = the entries with a tile (the dropped ones sort after them)
   // (an asynchronous build's counters snapshot for rt_hip_stats, where no build writes)
   HIP_TRY(rt_cand_bounds(c->d_cand_keys2, total, c->d_cand_start, (uint32_t)nt, async ? c->d_cand_ctr : nullptr, s));
-  if (RT_COMPACT_LISTS && c->cand_refine && !compat && !kept_now && (!kept_same || est_shape) &&
+  if (c->cand_refine && !compat && !kept_now && (!kept_same || est_shape) &&
       !(c->kept_pending && c->kept_pend.same(f, kp->rank, kp->nranks))) {
     // this frame's kept count -- and after an estimated-shape build its
     // counters (bounds_kernel's snapshot) -- for the later builds, read back
@@ -861,7 +842,7 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
   // a slice produced before for this frame is built without the mid-build
   // read-back (its sizes are deterministic); the read-back of the counts at
   // the end checks them, and a mismatch -- never expected -- builds again
-  const bool async = RT_DEV_SCAN && c->async_lists && !c->cand_store_fp && c->pknown.same(f, rank, nranks);
+  const bool async = c->async_lists && !c->cand_store_fp && c->pknown.same(f, rank, nranks);
   uint32_t total = 0, nglobal = 0;
   rc = cand_build(c, cp, s, (uint32_t)nranks, &total, &nglobal, async ? &c->pknown : nullptr,
                   async ? nullptr : &c->pknown);
@@ -875,7 +856,7 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
   // stable sort by tile gives each tile the same entries as the rank's own
   // build -- in the producers' interleaved slice order, not necessarily the
   // same order within a tile, which the render does not depend on (the
-  // winner is the lexicographic (new_dist, prim) minimum, rt_render.hip
+  // winner is the lexicographic (new_dist, prim) minimum, rt_isect.h
   // consider_exact)
   const int tbits = key_bits((size_t)tpr + 1);
   if (nranks > 256 || tbits + key_bits((size_t)nranks + 1) > 32)

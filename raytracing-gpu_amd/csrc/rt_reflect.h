@@ -19,7 +19,7 @@ struct ReflParams {
   const float4* node;  // octree nodes (2 float4 each, host/rt_cull.h)
   uint32_t nnode;
   const float4* rec;   // leaf-order triangle records (3 float4 each)
-  float4* node_rf;     // out: 3 float4 per node (rt_render.hip RfNode)
+  float4* node_rf;     // out: 3 float4 per node (rt_walk_lane.h rf_bound)
   float* node_phi;     // scratch: the normal cone's half-angle per node (radians; >= pi/2: none)
   uint32_t* unbounded; // out: leaves holding a triangle no bound covers (their ancestors are always visited)
 };

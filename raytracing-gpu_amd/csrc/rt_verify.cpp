@@ -299,18 +299,8 @@ extern "C" int rt_hip_probe_closest(rt_hip_ctx* c, const float* origins, const f
   if (!c->d_tri_prim) return rt_set_error(RT_EINVAL, "no triangles");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  KParams p;
-  std::memset(&p, 0, sizeof p);
-  p.tri = c->d_tri;
-  p.node = c->d_node;
-  p.nrec = c->nrec;
-  p.tri_prim = c->d_tri_prim;
-  p.spill = c->d_spill;
-  p.scene_c = rt::f3{c->scene_c[0], c->scene_c[1], c->scene_c[2]};
-  p.scene_r = c->scene_r;
-  p.scene_cmag = std::fmax(std::fabs(c->scene_c[0]), std::fmax(std::fabs(c->scene_c[1]),
-                                                               std::fabs(c->scene_c[2])));
-  p.eps_rel = c->eps_ulps * 5.9604645e-8f;  // the secondary rays' slack (make_ray at depth > 0)
+  // (the probe queries at eps_rel: the secondary rays' slack, make_ray at depth > 0)
+  KParams p = scene_params(c);
   if (!brute && c->exact_refl) {  // the exact reflection mode's walk
     int rc0 = reflect_prepare(c, s);
     if (rc0) return rc0;
@@ -366,17 +356,8 @@ extern "C" int rt_hip_probe_shadows(rt_hip_ctx* c, unsigned light, const float* 
     if (!c->d_lbuf) return rt_set_error(RT_EINVAL, "no light buffers (octree contexts with light buffers on)");
   }
   if (!c->d_tri_prim) return rt_set_error(RT_EINVAL, "no triangles");
-  KParams p;
-  std::memset(&p, 0, sizeof p);
-  p.light = c->d_light;
-  p.nlight = c->nlight;
-  p.tri_prim = c->d_tri_prim;
+  KParams p = scene_params(c);
   p.lbuf = brute ? nullptr : c->d_lbuf;
-  p.scene_c = rt::f3{c->scene_c[0], c->scene_c[1], c->scene_c[2]};
-  p.scene_r = c->scene_r;
-  p.scene_cmag = std::fmax(std::fabs(c->scene_c[0]), std::fmax(std::fabs(c->scene_c[1]),
-                                                               std::fabs(c->scene_c[2])));
-  p.eps_rel = c->eps_ulps * 5.9604645e-8f;
   float* d_o = nullptr;
   uint32_t* d_h = nullptr;
   std::vector<uint32_t> h(n);

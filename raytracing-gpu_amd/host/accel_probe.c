@@ -6,7 +6,7 @@
  * cross-check conservative culling: every sampled query's winner (new_dist,
  * prim) is compared with the brute-force winner over all triangles (the
  * reference's collide(), cpu/hit.c:72-91).  The traversal mirrors
- * csrc/rt_render.hip oct_closest(): same slab test with the same per-ray
+ * csrc/rt_walk_lane.h oct_closest(): same slab test with the same per-ray
  * slack, same front-to-back order, same pruning rule.  Not on the render path.
  */
 #define _GNU_SOURCE
@@ -21,7 +21,7 @@
 
 typedef struct { float dist; uint32_t prim; rt_vec3 pt; } winner;
 
-/* the device walk's box test and prune rule (csrc/rt_render.hip box_enter,
+/* the device walk's box test and prune rule (csrc/rt_walk_lane.h box_enter,
  * rt_prune), on the shared rt_cull.h arithmetic */
 static float probe_box_enter(rt_vec3 o, rt_vec3 inv, float eps, float lx, float ly, float lz,
                              float hx, float hy, float hz)
@@ -77,7 +77,7 @@ static void consider(rt_vec3 o, rt_vec3 d, rt_vec3 nd, float dlen, const float *
   }
 }
 
-/* any-hit walk of a shadow ray (mirrors oct_any in csrc/rt_render.hip) */
+/* any-hit walk of a shadow ray (mirrors oct_any in csrc/rt_walk_lane.h) */
 static int probe_any(const rt_flat_scene *f, rt_vec3 o, rt_vec3 d, float eps, uint32_t *stk,
                      unsigned long long *nodes, unsigned long long *tris)
 {
@@ -326,7 +326,7 @@ int rt_accel_probe(const rt_scene *s, int accel, int sample_stride, int check,
             }
             else
             {
-              /* same far-to-near octant push order as csrc/rt_render.hip */
+              /* same far-to-near octant push order as csrc/rt_walk_lane.h */
               uint32_t mask = RT_NODE_MASK(info);
               for (int j = 7; j >= 0; --j)
               {

@@ -1,6 +1,6 @@
 /*
  * rt_cull.h -- octree node encoding and the conservative culling arithmetic,
- * shared verbatim by the device traversal (csrc/rt_render.hip) and its host
+ * shared verbatim by the device traversal (csrc/rt_walk_lane.h, csrc/rt_walk_wave.h) and its host
  * model (host/accel_probe.c), so both make the same keep/cull decision on
  * the same floats (both are built with -ffp-contract=off).
  *

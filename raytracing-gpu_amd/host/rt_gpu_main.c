@@ -2,7 +2,7 @@
  * rt_gpu_main.c -- the `rt_gpu` command line, drop-in for the reference's
  * gpu/rt (gpu/rt.cpp:56-97): `rt_gpu file.svati output.png`, exactly two
  * arguments (the same usage error), gpu/rt's output semantics (3x3
- * supersampling, uint8 colours, <= 11 bounces, RGBA PNG; csrc/rt_render.hip
+ * supersampling, uint8 colours, <= 11 bounces, RGBA PNG; csrc/rt_compat.h
  * compat_kernel).  An optional third argument `--accel flat|octree|octree_gpu`
  * picks the acceleration (default: by scene size, as `rt`).
  */

@@ -380,7 +380,7 @@ def test_synthetic_c5_exact_on_sampled_tiles(gpu):
 
 
 # Traversal policies of the octree walk (rt_hip_set_policy, one kernel each;
-# csrc/rt_render.hip): default (staged packet closest hit for coherent
+# closest_q / shadow_q in csrc/rt_query.h): default (staged packet closest hit for coherent
 # queries, per-lane otherwise), all per-lane, all staged packet, default +
 # staged directional-light shadows.  The default runs in every other test.
 TRAV = [0, 1, 2, 3]
