@@ -25,7 +25,9 @@
 #include "rt_build.h"
 #include "rt_cand.h"
 #include "rt_kernels.h"
+#include "rt_forecast.h"
 #include "rt_lightbuf.h"
+#include "rt_mem.h"
 #include "rt_shadow.h"
 #include "rt_reflect.h"
 #include "rt_tiles.h"
@@ -69,28 +71,14 @@ static constexpr size_t kCostBytes = 64;  // the trace's item-clock sum (KParams
 static constexpr size_t kFrameCounterBytes =
     kItemCounterBytes + kStatBytes + kHitCounterBytes + kCostBytes;
 
-// The sizes of one list build, which are deterministic for its (camera
-// frame, rank, nranks): a later build of the same frame sizes its buffers and
-// launches from them instead of reading its own back (async_lists).
-struct ListShape {
-  int valid = 0;
-  rt_frame frame{};
-  int rank = -1, nranks = 0;
-  uint32_t total = 0, nglobal = 0;           // entries, global prims
-  uint32_t nbig = 0, nitems = 0, over = 0;   // the big-emission launch shape
-  bool same(const rt_frame* f, int r, int n) const {
-    return valid && rank == r && nranks == n && std::memcmp(&frame, f, sizeof *f) == 0;
-  }
-  // the same image size and rank split (the same tiles), any camera
-  bool same_grid(const rt_frame* f, int r, int n) const {
-    return valid && rank == r && nranks == n && frame.width == f->width && frame.height == f->height;
-  }
-  void set(const rt_frame* f, int r, int n) {
-    valid = 1;
-    frame = *f;
-    rank = r;
-    nranks = n;
-  }
+// The context's stream, declared before the buffers so that it is destroyed
+// after them (members go in reverse order of declaration).
+struct StreamOwner {
+  hipStream_t s = nullptr;
+  StreamOwner() = default;
+  StreamOwner(const StreamOwner&) = delete;
+  ~StreamOwner() { if (s) (void)hipStreamDestroy(s); }
+  operator hipStream_t() const { return s; }
 };
 
 struct rt_hip_ctx {
@@ -98,16 +86,16 @@ struct rt_hip_ctx {
   int accel = RT_ACCEL_FLAT;
   int count_work = 0;
   int grid = 0;
-  hipStream_t stream = nullptr;
+  StreamOwner stream;
   hipStream_t last_stream = nullptr;
-  float4* d_tri = nullptr;
-  float* d_nrm = nullptr;
-  float* d_mat = nullptr;
-  float* d_light = nullptr;
-  float4* d_node = nullptr;
-  uint32_t* d_counter = nullptr;
-  unsigned long long* d_stats = nullptr;
-  uint2* d_spill = nullptr;
+  DevBuf<float4> d_tri;
+  DevBuf<float> d_nrm;
+  DevBuf<float> d_mat;
+  DevBuf<float> d_light;
+  DevBuf<float4> d_node;
+  DevBuf<uint32_t> d_counter;
+  unsigned long long* d_stats = nullptr;  // view: into d_counter, past the item counters
+  DevBuf<uint2> d_spill;
   uint32_t nrec = 0, nlight = 0;
   rt_accel_info info{};
   float scene_c[3]{}, scene_r = 0;
@@ -115,22 +103,23 @@ struct rt_hip_ctx {
   float eps_ulps = RT_EPS_ULPS_DEFAULT;
   float cam_eps_ulps = RT_CAM_EPS_ULPS_DEFAULT;
   int policy = RT_POLICY_DEFAULT;  // traversal policy (tests / A/B only: rt_hip_set_policy)
-  unsigned long long* d_tile_cycles = nullptr;  // COUNT pass: per-item clocks
+  DevBuf<unsigned long long> d_tile_cycles;  // COUNT pass: per-item clocks
   // wavefront split (rt_render.hip): hit records of RT_HIT_REGIONS regions
-  float4* d_hit = nullptr;          // 2 float4 per record
-  uint32_t* d_hit_prev = nullptr;   // per record
-  float4* d_hit_term = nullptr;     // per record
-  uint32_t* d_hit_count = nullptr;  // RT_HIT_REGIONS append counters + as many shade chunk counters
-  size_t hit_cap = 0;               // records per region
+  DevBuf<float4> d_hit;          // 2 float4 per record
+  DevBuf<uint32_t> d_hit_prev;   // per record
+  DevBuf<float4> d_hit_term;     // per record
+  uint32_t* d_hit_count = nullptr;  // view: into d_counter, RT_HIT_REGIONS append counters + as many shade chunk counters
+  // records per region that all three record buffers hold (0 while one is missing)
+  size_t hit_cap() const {
+    return std::min({d_hit.cap() / 2, d_hit_prev.cap(), d_hit_term.cap()}) / RT_HIT_REGIONS;
+  }
   size_t hit_need = 0;              // per region: what the last overflowing frame needed
-  uint32_t* d_last = nullptr;       // per (item, lane): a path's deepest record
-  size_t last_cap = 0;              // items
+  DevBuf<uint32_t> d_last;          // per (item, lane): a path's deepest record
   // G-buffer (rt_hip_set_gbuffer): the capturing trace's record per (item,
   // lane), and the frame whose render filled it (gb_valid: rt_hip_gbuffer may
   // read it; rank / nranks / stream are last_p's and last_stream)
   int gbuffer = 0;
-  uint4* d_capture = nullptr;
-  size_t capture_cap = 0;           // items
+  DevBuf<uint4> d_capture;
   int gb_valid = 0;
   rt_frame gb_frame{};
 // per-rank candidate lists built without a host read-back (VERDICT r04
@@ -145,23 +134,23 @@ struct rt_hip_ctx {
   // light buffers (csrc/rt_lightbuf.hip), built for the slack lb_ulps
   int light_buffers = 1;            // rt_hip_set_light_buffers
   std::vector<LBDevice*> lb_dev;    // per light (nullptr: the walk)
-  RtLightBuf* d_lbuf = nullptr;     // per light, device
+  DevBuf<RtLightBuf> d_lbuf;     // per light, device
   float lb_ulps = -1.0f;
   int lb_proven = -1;               // built proven (exact_shadows) or slack-grown
   unsigned long long lb_entry_cap = 0;  // test hook: fail builds past this many entries (0: none)
-  KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows)
+  KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here
   // exact shadow rays (csrc/rt_shadow.hip), built for the slack sh_ulps
-  float2* d_prim_mu = nullptr;
-  float2* d_node_mu = nullptr;
-  uint4* d_oob = nullptr;       // exact-shadow mode: deferred off-box shadow queries
-  uint32_t* d_oob_count = nullptr;
-  unsigned long long* d_frame_check = nullptr;  // KParams::frame_check: sticky per-frame checks (rt_hip_frame_check)
-  uint32_t* d_sh_global = nullptr;
+  DevBuf<float2> d_prim_mu;
+  DevBuf<float2> d_node_mu;
+  DevBuf<uint4> d_oob;       // exact-shadow mode: deferred off-box shadow queries
+  DevBuf<uint32_t> d_oob_count;
+  DevBuf<unsigned long long> d_frame_check;  // KParams::frame_check: sticky per-frame checks (rt_hip_frame_check)
+  DevBuf<uint32_t> d_sh_global;
   uint32_t n_sh_global = 0;
   // exact reflection rays (csrc/rt_reflect.hip, rt_hip_set_exact_reflections):
   // per-node error-region bounds, built once per tree when the mode is enabled
   int exact_refl = 0;
-  float4* d_node_rf = nullptr;
+  DevBuf<float4> d_node_rf;
   unsigned long long rf_unbounded = 0;  // leaves holding a triangle no bound covers
   float sh_ulps = -1.0f;
   float sh_omax = 0.0f;
@@ -169,7 +158,7 @@ struct rt_hip_ctx {
   // shadow rays exact by proof (rt_hip_set_exact_shadows, default on): proven
   // light buffers, the per-node multiplier walk where a light has none
   int exact_shadows = 1;
-  size_t tile_cycles_cap = 0, tile_cycles_n = 0;
+  size_t tile_cycles_n = 0;         // items of the last work-counting pass (d_tile_cycles: 6 per item)
   // exact camera rays (csrc/rt_cand.hip)
   int exact_camera = 1;
   // the big footprints' entries refined per tile (rt_hip_set_camera_refine,
@@ -178,77 +167,63 @@ struct rt_hip_ctx {
 #define RT_CAND_REFINE_DEFAULT 1
 #endif
   int cand_refine = RT_CAND_REFINE_DEFAULT;
-  const uint32_t* d_cand_valid = nullptr;  // device word: the last built lists' entries with a tile
+  // view: the device word holding the last built lists' entries with a tile
+  // (d_cand_start[ntiles], or its saved copy d_cand_ctr[8])
+  const uint32_t* d_cand_valid = nullptr;
   double bound_scale = 1.0;  // 1 = the proven float-MT error bound (tools/mt_bound.py)
-  float4* d_tri_prim = nullptr;  // prim-order records (== d_tri for FLAT)
+  float4* d_tri_prim = nullptr;  // view: prim-order records, d_tri (FLAT) or d_tri_prim_own
+  DevBuf<float4> d_tri_prim_own;
   uint32_t nprim = 0;
-  uint32_t* d_cand_list = nullptr;    // nprim
-  void* d_cand_fp = nullptr;          // nprim footprints (rt_cand_footprint_bytes each)
-  uint4* d_cand_sfp = nullptr;        // 2 nprim: compact small footprints (CandParams::sfp)
+  DevBuf<uint32_t> d_cand_list;    // nprim
+  DevBuf<void> d_cand_fp;          // nprim footprints (rt_cand_footprint_bytes each)
+  DevBuf<uint4> d_cand_sfp;        // 2 nprim: compact small footprints (CandParams::sfp)
   int cand_store_fp = 0;              // keep every footprint (rt_hip_cand_verify's re-derivation)
-  uint32_t* d_cand_visits = nullptr;  // nprim + 1
-  uint32_t* d_cand_off = nullptr;     // nprim + 1
-  uint32_t* d_cand_start = nullptr;   // ntiles + 1
-  uint32_t* d_cand_keys = nullptr;    // entries (tile), emit order
-  uint32_t* d_cand_keys2 = nullptr;   // entries (tile), sorted
-  uint32_t* d_cand_vals = nullptr;    // entries (prim), emit order
-  uint32_t* d_cand_global = nullptr;  // nprim
-  uint32_t* d_cand_big = nullptr;     // nprim
-  uint32_t* d_cand_ctr = nullptr;     // 4
-  float* d_cand_skip = nullptr;       // nprim
-  uint32_t* d_cand_big_lane = nullptr;  // kBigLaneCap x 64 lane subtotals of big footprints
-  uint2* d_cand_items = nullptr;        // kItemCap big-emission work items
-  uint32_t* d_cand_wave_items = nullptr;  // rt_cand_big_waves() + 1 each: items per big_count wave,
-  uint32_t* d_cand_wave_base = nullptr;   // and their exclusive scan
-  uint32_t* d_scan_bsum = nullptr;        // rt_cand_scan_dev_tiles(nprim) tile sums of the device-length scans
+  DevBuf<uint32_t> d_cand_visits;  // nprim + 1
+  DevBuf<uint32_t> d_cand_off;     // nprim + 1
+  DevBuf<uint32_t> d_cand_start;   // ntiles + 1
+  DevBuf<uint32_t> d_cand_keys;    // entries (tile), emit order
+  DevBuf<uint32_t> d_cand_keys2;   // entries (tile), sorted
+  DevBuf<uint32_t> d_cand_vals;    // entries (prim), emit order
+  DevBuf<uint32_t> d_cand_global;  // nprim
+  DevBuf<uint32_t> d_cand_big;     // nprim
+  DevBuf<uint32_t> d_cand_ctr;     // 32: [0..7] the build's counters, [8] a saved valid count, [16..23] the last asynchronous build's
+  DevBuf<float> d_cand_skip;       // nprim
+  DevBuf<uint32_t> d_cand_big_lane;  // kBigLaneCap x 64 lane subtotals of big footprints
+  DevBuf<uint2> d_cand_items;        // kItemCap big-emission work items
+  DevBuf<uint32_t> d_cand_wave_items;  // rt_cand_big_waves() + 1 each: items per big_count wave,
+  DevBuf<uint32_t> d_cand_wave_base;   // and their exclusive scan
+  DevBuf<uint32_t> d_scan_bsum;        // rt_cand_scan_dev_tiles(nprim) tile sums of the device-length scans
   uint32_t cand_item_cap = 0xffffffffu;  // test hook: fewer items (min with kItemCap)
-  uint32_t* d_prim_leaf = nullptr;    // nprim: a leaf holding each prim (camera-independent)
-  uint32_t* d_cand = nullptr;
-  uint32_t* d_order = nullptr;        // 3 x (ntiles + 1): heavy flags, their scan, the work order
-  size_t cand_cap = 0, cand_tiles_cap = 0, order_cap = 0;
-  void* d_scan_tmp = nullptr;
-  size_t scan_tmp_bytes = 0;
-  uint32_t* h_cand = nullptr;  // pinned: a read-back build's ctr[0..7] (rt_cand.h CandParams::ctr)
+  DevBuf<uint32_t> d_prim_leaf;    // nprim: a leaf holding each prim (camera-independent)
+  DevBuf<uint32_t> d_cand;
+  DevBuf<uint32_t> d_order;        // 3 x (ntiles + 1): heavy flags, their scan, the work order
+  DevBuf<void> d_scan_tmp;
+  PinnedBuf<uint32_t> h_cand;  // pinned: a read-back build's ctr[0..7] (rt_cand.h CandParams::ctr)
   // asynchronous per-rank builds (no host read-back in the render path): the
   // entry buffers are sized from an earlier frame's total, read back without
   // waiting when its build has finished
   int async_lists = RT_ASYNC_LISTS_DEFAULT;
-  // the frame (camera frame, rank, nranks) whose per-rank lists were last
-  // built with a read-back, and their sizes: the same frame's lists are
-  // deterministic, so they are rebuilt without reading the total back
-  ListShape known;
-  ListShape pknown;  // the same for the last read-back produce (rt_hip_cand_produce)
+  // which builds run without that read-back, the compaction's size and the
+  // late read-back of a build's kept count and counters (h_kept, ev_kept)
+  ListForecast forecast;
+  ListShape pknown;  // the sizes of the last read-back produce (rt_hip_cand_produce) and its frame
+  PinnedBuf<uint32_t> h_kept;  // pinned: [0] the kept count, [1..8] an asynchronous build's counters ctr[0..7]
+  hipEvent_t ev_kept = nullptr;
   // the frame (camera frame, rank, nranks) whose trace last recorded its
   // per-item clocks (d_item_cost, their sum in the frame counters) and its
   // grid: the same frame's next work order puts its long items first
-  // the entries the refinement kept (start[ntiles]) in the last build of
-  // kept_for's frame, read back without waiting (h_kept, ev_kept): the same
-  // frame's asynchronous builds compact the entries to that many before the
-  // sort instead of sorting the dropped ones too
-  ListShape kept_for;
-  uint32_t* h_kept = nullptr;   // pinned: [0] the kept count, [1..8] an asynchronous build's counters ctr[0..7]
-  hipEvent_t ev_kept = nullptr;
-  int snap_pending = 0;         // h_kept[1..8] will hold the last estimated-shape build's counters (ev_kept)
-  int kept_ready = 0;           // kept holds kept_for's count
-  ListShape kept_pend;          // the frame whose kept count is on its way into h_kept[0] (ev_kept)
-  int kept_pending = 0;
-  uint32_t kept = 0;
   ListShape cost_hist;
   uint32_t cost_waves = 0;
-  uint32_t* d_item_cost = nullptr;  // 4 x ntiles_local
-  size_t item_cost_cap = 0;
+  DevBuf<uint32_t> d_item_cost;  // 4 x ntiles_local
   int last_async = 0;                 // the last render's lists came from an asynchronous build
   unsigned long long cand_prims = 0, cand_entries = 0, cand_global = 0;
   // triangle-parallel lists (rt_hip_cand_produce / rt_hip_cand_consume)
-  uint32_t* d_send = nullptr;   // 3 words per routed entry, destination-rank order
-  size_t send_cap = 0;          // words
+  DevBuf<uint32_t> d_send;   // 3 words per routed entry, destination-rank order
   uint32_t send_n = 0;          // entries of the last produce
-  uint32_t* d_part = nullptr;    // the partition's per-wave rank counts and their scan
-  size_t part_cap = 0;          // words
-  uint32_t* d_rstart = nullptr;  // nranks + 1 first entries per destination
-  uint32_t* h_rstart = nullptr;  // pinned copy
-  size_t rstart_cap = 0;
-  KParams ext{};                // the consumed lists' kernel parameters
+  DevBuf<uint32_t> d_part;    // the partition's per-wave rank counts and their scan
+  DevBuf<uint32_t> d_rstart;  // nranks + 1 first entries per destination
+  PinnedBuf<uint32_t> h_rstart;  // pinned copy
+  KParams ext{};                // the consumed lists' kernel parameters (views into the entry, offset and order buffers)
   int ext_ready = 0, ext_rank = -1, ext_nranks = 0;
   rt_frame ext_frame{};         // the frame they were built for (compared bytewise)
   uint32_t ext_total = 0;
@@ -258,13 +233,22 @@ struct rt_hip_ctx {
   int timing = 0;
   hipEvent_t ev[RT_TIMED_FRAMES][5] = {};  // lists | trace | shade | fold |
   unsigned long long frames = 0;  // timed frames recorded
+
+  // the light buffers and the events; then the members: every buffer, and
+  // the stream (declared first) last.  The caller has set the device.
+  ~rt_hip_ctx() {
+    for (LBDevice* d : lb_dev) rt_lightbuf_free(d);
+    if (ev_kept) (void)hipEventDestroy(ev_kept);
+    for (auto& f : ev)
+      for (hipEvent_t e : f)
+        if (e) (void)hipEventDestroy(e);
+  }
 };
 
-// A setting that changes the lists: no earlier build's sizes or kept count
-// apply any more (the read-backs on their way are discarded too)
+// A setting that changes the lists (ListForecast::reset)
 static inline void lists_changed(rt_hip_ctx* c) {
-  c->known.valid = c->pknown.valid = c->kept_for.valid = 0;
-  c->kept_pending = c->snap_pending = 0;
+  c->forecast.reset();
+  c->pknown.valid = 0;
 }
 
 // The unit of the culling slacks: eps_ulps of them, relative to the

@@ -31,73 +31,15 @@ extern "C" int rt_hip_device_count(int* n) {
 }
 
 template <class T>
-static int upload(T** dst, const void* src, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  HIP_TRY(hipMalloc((void**)dst, bytes));
-  if (src) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+static int upload(DevBuf<T>& dst, const void* src, size_t bytes) {
+  HIP_TRY(dst.alloc(bytes / sizeof(T)));
+  if (src && bytes) HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
   return RT_OK;
 }
 
 extern "C" void rt_hip_destroy(rt_hip_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)hipFree(c->d_tri);
-  (void)hipFree(c->d_nrm);
-  (void)hipFree(c->d_mat);
-  (void)hipFree(c->d_light);
-  (void)hipFree(c->d_node);
-  (void)hipFree(c->d_counter);  // also holds d_stats and d_hit_count (kFrameCounterBytes)
-  (void)hipFree(c->d_spill);
-  (void)hipFree(c->d_tile_cycles);
-  (void)hipFree(c->d_hit);
-  (void)hipFree(c->d_hit_prev);
-  (void)hipFree(c->d_hit_term);
-  (void)hipFree(c->d_last);
-  (void)hipFree(c->d_capture);
-  (void)hipFree(c->d_prim_mu);
-  (void)hipFree(c->d_node_mu);
-  (void)hipFree(c->d_oob);
-  (void)hipFree(c->d_oob_count);
-  (void)hipFree(c->d_frame_check);
-  (void)hipFree(c->d_node_rf);
-  (void)hipFree(c->d_sh_global);
-  for (LBDevice* d : c->lb_dev) rt_lightbuf_free(d);
-  (void)hipFree(c->d_lbuf);
-  if (c->d_tri_prim != c->d_tri) (void)hipFree(c->d_tri_prim);
-  (void)hipFree(c->d_cand_list);
-  (void)hipFree(c->d_cand_fp);
-  (void)hipFree(c->d_cand_sfp);
-  (void)hipFree(c->d_cand_visits);
-  (void)hipFree(c->d_cand_off);
-  (void)hipFree(c->d_cand_start);
-  (void)hipFree(c->d_cand_keys);
-  (void)hipFree(c->d_cand_keys2);
-  (void)hipFree(c->d_cand_vals);
-  (void)hipFree(c->d_cand_global);
-  (void)hipFree(c->d_cand_big);
-  (void)hipFree(c->d_cand_ctr);
-  (void)hipFree(c->d_cand_big_lane);
-  (void)hipFree(c->d_cand_items);
-  (void)hipFree(c->d_cand_wave_items);
-  (void)hipFree(c->d_cand_wave_base);
-  (void)hipFree(c->d_scan_bsum);
-  (void)hipFree(c->d_cand_skip);
-  (void)hipFree(c->d_prim_leaf);
-  (void)hipFree(c->d_cand);
-  (void)hipFree(c->d_order);
-  (void)hipFree(c->d_scan_tmp);
-  if (c->h_cand) (void)hipHostFree(c->h_cand);
-  (void)hipFree(c->d_send);
-  (void)hipFree(c->d_rstart);
-  (void)hipFree(c->d_part);
-  (void)hipFree(c->d_item_cost);
-  if (c->h_kept) (void)hipHostFree(c->h_kept);
-  if (c->ev_kept) (void)hipEventDestroy(c->ev_kept);
-  if (c->h_rstart) (void)hipHostFree(c->h_rstart);
-  for (auto& f : c->ev)
-    for (hipEvent_t e : f)
-      if (e) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -109,12 +51,12 @@ int shadow_prepare(rt_hip_ctx* c, hipStream_t s) {
   if (c->d_node_mu && c->sh_ulps == c->eps_ulps) return RT_OK;
   const size_t np = c->nprim, nn = c->info.nodes;
   if (!c->d_node_mu) {
-    HIP_TRY(hipMalloc((void**)&c->d_prim_mu, (np + 1) * sizeof(float2)));
-    HIP_TRY(hipMalloc((void**)&c->d_sh_global, (np + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_node_mu, (nn + 1) * sizeof(float2)));
+    HIP_TRY(c->d_prim_mu.alloc(np + 1));
+    HIP_TRY(c->d_sh_global.alloc(np + 1));
+    HIP_TRY(c->d_node_mu.alloc(nn + 1));
   }
-  uint32_t* d_n = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_n, sizeof(uint32_t)));
+  DevBuf<uint32_t> d_n;
+  HIP_TRY(d_n.alloc(1));
   ShadowParams sp;
   std::memset(&sp, 0, sizeof sp);
   sp.tri = c->d_tri_prim;
@@ -143,13 +85,11 @@ int shadow_prepare(rt_hip_ctx* c, hipStream_t s) {
   sp.nglobal = d_n;
   uint32_t n = 0;
   std::vector<float2> nm(1);
-  hipError_t he = hipMemsetAsync(d_n, 0, sizeof(uint32_t), s);
-  if (he == hipSuccess) he = rt_shadow_build(&sp, (int)c->info.max_depth + 2, s);
-  if (he == hipSuccess) he = hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, s);
-  if (he == hipSuccess) he = hipMemcpyAsync(nm.data(), c->d_node_mu, sizeof(float2), hipMemcpyDeviceToHost, s);
-  if (he == hipSuccess) he = hipStreamSynchronize(s);
-  (void)hipFree(d_n);
-  if (he != hipSuccess) return rt_set_error(RT_EHIP, "shadow multipliers: %s", hipGetErrorString(he));
+  HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(uint32_t), s));
+  HIP_TRY(rt_shadow_build(&sp, (int)c->info.max_depth + 2, s));
+  HIP_TRY(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(nm.data(), c->d_node_mu, sizeof(float2), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   c->n_sh_global = n;
   c->sh_omax = (float)(sp.omax_assumed * (1.0 - 1e-6));
   c->sh_mu_max = nm[0].x;  // the root's: the max over the scene
@@ -168,8 +108,7 @@ static void lbuf_release(rt_hip_ctx* c) {
     rt_lightbuf_free(d);
     d = nullptr;
   }
-  (void)hipFree(c->d_lbuf);
-  c->d_lbuf = nullptr;
+  c->d_lbuf.reset();
   c->lb_ulps = -1.0f;
 }
 
@@ -273,7 +212,7 @@ int lbuf_prepare(rt_hip_ctx* c, hipStream_t s) {
     }
   }
   c->info.lightbuf_failed = failed;
-  HIP_TRY(hipMalloc((void**)&c->d_lbuf, hb.size() * sizeof(RtLightBuf)));
+  HIP_TRY(c->d_lbuf.alloc(hb.size()));
   HIP_TRY(hipMemcpy(c->d_lbuf, hb.data(), hb.size() * sizeof(RtLightBuf), hipMemcpyHostToDevice));
   c->lb_ulps = c->eps_ulps;
   c->lb_proven = c->exact_shadows;
@@ -344,20 +283,20 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
   size_t bytes_mat = fs.nobj * RT_MAT_FLOATS * sizeof(float);
   size_t bytes_light = fs.nlight * RT_LIGHT_FLOATS * sizeof(float);
   size_t bytes_node = fs.nnode * RT_NODE_FLOATS * sizeof(float);
-  rc = upload(&c->d_tri, fs.tri, bytes_tri);
-  if (!rc) rc = upload(&c->d_nrm, fs.nrm, bytes_nrm);
-  if (!rc) rc = upload(&c->d_mat, fs.mat, bytes_mat);
-  if (!rc) rc = upload(&c->d_light, fs.light, bytes_light);
-  if (!rc && fs.nnode) rc = upload(&c->d_node, fs.node, bytes_node);
+  rc = upload(c->d_tri, fs.tri, bytes_tri);
+  if (!rc) rc = upload(c->d_nrm, fs.nrm, bytes_nrm);
+  if (!rc) rc = upload(c->d_mat, fs.mat, bytes_mat);
+  if (!rc) rc = upload(c->d_light, fs.light, bytes_light);
+  if (!rc && fs.nnode) rc = upload(c->d_node, fs.node, bytes_node);
   // the per-frame counters in one allocation, zeroed by one memset per frame:
   // 8 item-stream counters (rt_render.hip), the stats, the hit-record and
   // shade-chunk counters
-  if (!rc) rc = upload(&c->d_counter, nullptr, kFrameCounterBytes);
+  if (!rc) rc = upload(c->d_counter, nullptr, kFrameCounterBytes);
   if (!rc) {
-    c->d_stats = (unsigned long long*)((char*)c->d_counter + kItemCounterBytes);
-    c->d_hit_count = (uint32_t*)((char*)c->d_counter + kItemCounterBytes + kStatBytes);
+    c->d_stats = (unsigned long long*)((char*)c->d_counter.get() + kItemCounterBytes);
+    c->d_hit_count = (uint32_t*)((char*)c->d_counter.get() + kItemCounterBytes + kStatBytes);
   }
-  if (!rc && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
+  if (!rc && hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking) != hipSuccess)
     rc = rt_set_error(RT_EHIP, "hipStreamCreate");
   rt_device_tree tree{};
   if (!rc && dev_build && fs.ntri) {
@@ -374,9 +313,10 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
     } else {
       // leaf-order records for the walk; the prim-order ones stay for the
       // camera candidate lists
-      c->d_tri_prim = c->d_tri;
-      c->d_tri = tree.tri;
-      c->d_node = tree.node;
+      c->d_tri_prim_own = std::move(c->d_tri);
+      c->d_tri_prim = c->d_tri_prim_own;
+      c->d_tri.adopt(tree.tri, (size_t)tree.nref * RT_TRI_FLOATS / 4);
+      c->d_node.adopt(tree.node, (size_t)tree.nnode * RT_NODE_FLOATS / 4);
       c->nrec = tree.nref;
       bytes_tri = (size_t)tree.nref * RT_TRI_FLOATS * sizeof(float);
       bytes_node = (size_t)tree.nnode * RT_NODE_FLOATS * sizeof(float);
@@ -396,7 +336,8 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
       rt_flat_scene fp;  // host octree: records are leaf order, with duplicates
       rc = rt_flatten(scene, RT_ACCEL_FLAT, &fp);
       if (!rc) {
-        rc = upload(&c->d_tri_prim, fp.tri, fp.nrec * RT_TRI_FLOATS * sizeof(float));
+        rc = upload(c->d_tri_prim_own, fp.tri, fp.nrec * RT_TRI_FLOATS * sizeof(float));
+        c->d_tri_prim = c->d_tri_prim_own;
         rt_flat_free(&fp);
       }
     }
@@ -454,7 +395,7 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
   c->info.scene_radius = c->scene_r;
   // per-lane traversal stack spill area, [entry][lane] for the largest grid
   if (c->accel == RT_ACCEL_OCTREE &&
-      hipMalloc((void**)&c->d_spill, (size_t)gmax * 64 * RT_SPILL_STACK * sizeof(uint2)) != hipSuccess) {
+      c->d_spill.alloc((size_t)gmax * 64 * RT_SPILL_STACK) != hipSuccess) {
     rt_hip_destroy(c);
     return rt_set_error(RT_EHIP, "hipMalloc traversal spill stack");
   }
@@ -512,14 +453,13 @@ extern "C" int rt_hip_set_exact_shadows(rt_hip_ctx* c, int enable) {
 
 // The exact reflection walk's per-node bounds (csrc/rt_reflect.hip): once
 // per tree, synchronous (setup).
-int reflect_prepare(rt_hip_ctx* c, hipStream_t s) {
-  if (c->d_node_rf || c->accel != RT_ACCEL_OCTREE || !c->d_node) return RT_OK;
+static int reflect_build(rt_hip_ctx* c, hipStream_t s) {
   const size_t nn = c->info.nodes;
-  float* phi = nullptr;
-  uint32_t* d_u = nullptr;
-  HIP_TRY(hipMalloc((void**)&c->d_node_rf, (3 * nn + 3) * sizeof(float4)));
-  hipError_t he = hipMalloc((void**)&phi, (nn + 1) * sizeof(float));
-  if (he == hipSuccess) he = hipMalloc((void**)&d_u, sizeof(uint32_t));
+  DevBuf<float> phi;
+  DevBuf<uint32_t> d_u;
+  HIP_TRY(c->d_node_rf.alloc(3 * nn + 3));
+  HIP_TRY(phi.alloc(nn + 1));
+  HIP_TRY(d_u.alloc(1));
   ReflParams rp;
   std::memset(&rp, 0, sizeof rp);
   rp.node = c->d_node;
@@ -529,20 +469,20 @@ int reflect_prepare(rt_hip_ctx* c, hipStream_t s) {
   rp.node_phi = phi;
   rp.unbounded = d_u;
   uint32_t u = 0;
-  if (he == hipSuccess) he = hipMemsetAsync(c->d_node_rf, 0, (3 * nn + 3) * sizeof(float4), s);
-  if (he == hipSuccess) he = hipMemsetAsync(d_u, 0, sizeof(uint32_t), s);
-  if (he == hipSuccess) he = rt_reflect_build(&rp, (int)c->info.max_depth + 2, s);
-  if (he == hipSuccess) he = hipMemcpyAsync(&u, d_u, sizeof u, hipMemcpyDeviceToHost, s);
-  if (he == hipSuccess) he = hipStreamSynchronize(s);
-  (void)hipFree(phi);
-  (void)hipFree(d_u);
-  if (he != hipSuccess) {
-    (void)hipFree(c->d_node_rf);
-    c->d_node_rf = nullptr;
-    return rt_set_error(RT_EHIP, "reflection bounds: %s", hipGetErrorString(he));
-  }
+  HIP_TRY(hipMemsetAsync(c->d_node_rf, 0, (3 * nn + 3) * sizeof(float4), s));
+  HIP_TRY(hipMemsetAsync(d_u, 0, sizeof(uint32_t), s));
+  HIP_TRY(rt_reflect_build(&rp, (int)c->info.max_depth + 2, s));
+  HIP_TRY(hipMemcpyAsync(&u, d_u, sizeof u, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   c->rf_unbounded = u;
   return RT_OK;
+}
+
+int reflect_prepare(rt_hip_ctx* c, hipStream_t s) {
+  if (c->d_node_rf || c->accel != RT_ACCEL_OCTREE || !c->d_node) return RT_OK;
+  const int rc = reflect_build(c, s);
+  if (rc) c->d_node_rf.reset();  // (its presence says "built")
+  return rc;
 }
 
 extern "C" int rt_hip_set_exact_reflections(rt_hip_ctx* c, int enable) {
@@ -581,36 +521,20 @@ extern "C" int rt_hip_set_camera_bound_scale(rt_hip_ctx* c, double scale) {
 // (item, lane).
 static int hit_buffers(rt_hip_ctx* c, size_t ntiles) {
   const size_t items = 4 * ntiles;
-  if (items > c->last_cap) {
-    (void)hipFree(c->d_last);
-    c->d_last = nullptr;
-    c->last_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->d_last, items * 64 * sizeof(uint32_t)));
-    c->last_cap = items;
-  }
-  if (c->gbuffer && items > c->capture_cap) {  // the capturing trace's record per (item, lane)
-    (void)hipFree(c->d_capture);
-    c->d_capture = nullptr;
-    c->capture_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->d_capture, items * 64 * sizeof(uint4)));
-    c->capture_cap = items;
-  }
+  HIP_TRY(c->d_last.grow(items * 64, items * 64));
+  if (c->gbuffer) HIP_TRY(c->d_capture.grow(items * 64, items * 64));  // the capturing trace's record per (item, lane)
   size_t want =(2 * items * 64 + RT_HIT_REGIONS - 1) / RT_HIT_REGIONS + 1024;
   if (c->hit_need > want) want = c->hit_need;
   if (want > (1ull << 29) - 1) want = (1ull << 29) - 1;  // slot field of a record index
-  if (want <= c->hit_cap && c->d_hit) return RT_OK;
-  (void)hipFree(c->d_hit);
-  (void)hipFree(c->d_hit_prev);
-  (void)hipFree(c->d_hit_term);
-  c->d_hit = nullptr;
-  c->d_hit_prev = nullptr;
-  c->d_hit_term = nullptr;
-  c->hit_cap = 0;
+  if (want <= c->hit_cap()) return RT_OK;
+  // all three or none: hit_cap() is what every one of them holds
+  c->d_hit.reset();
+  c->d_hit_prev.reset();
+  c->d_hit_term.reset();
   const size_t n = want * RT_HIT_REGIONS;
-  HIP_TRY(hipMalloc((void**)&c->d_hit, n * 2 * sizeof(float4)));
-  HIP_TRY(hipMalloc((void**)&c->d_hit_prev, n * sizeof(uint32_t)));
-  HIP_TRY(hipMalloc((void**)&c->d_hit_term, n * sizeof(float4)));
-  c->hit_cap = want;  // only once every buffer exists
+  HIP_TRY(c->d_hit.alloc(2 * n));
+  HIP_TRY(c->d_hit_prev.alloc(n));
+  HIP_TRY(c->d_hit_term.alloc(n));
   return RT_OK;
 }
 
@@ -700,17 +624,11 @@ static int render_buffers(rt_hip_ctx* c, KParams& p) {
   p.hit_term = c->d_hit_term;
   p.hit_count = c->d_hit_count;
   p.shade_counter = c->d_hit_count + RT_HIT_REGIONS * 32;
-  p.hit_cap = (uint32_t)c->hit_cap;
+  p.hit_cap = (uint32_t)c->hit_cap();
   p.last = c->d_last;
   if (c->count_work) {  // per-item clocks of the instrumented pass (rt_hip_tile_cycles)
     const size_t items = 4 * (size_t)p.ntiles_local;
-    if (items > c->tile_cycles_cap) {
-      (void)hipFree(c->d_tile_cycles);
-      c->d_tile_cycles = nullptr;
-      c->tile_cycles_cap = 0;
-      HIP_TRY(hipMalloc((void**)&c->d_tile_cycles, 6 * items * sizeof(unsigned long long)));
-      c->tile_cycles_cap = items;
-    }
+    HIP_TRY(c->d_tile_cycles.grow(6 * items, 6 * items));
     c->tile_cycles_n = items;
     p.tile_cycles = c->d_tile_cycles;
   }
@@ -739,8 +657,8 @@ static int render_shadows(rt_hip_ctx* c, KParams& p, hipStream_t s) {
   // re-shaded without the lights past the 32nd
   if (p.lbuf && c->exact_shadows && c->nlight <= 32) {
     if (!c->d_oob) {
-      HIP_TRY(hipMalloc((void**)&c->d_oob_count, sizeof(uint32_t)));
-      HIP_TRY(hipMalloc((void**)&c->d_oob, (size_t)RT_OOB_CAP * sizeof(uint4)));
+      HIP_TRY(c->d_oob_count.alloc(1));
+      HIP_TRY(c->d_oob.alloc(RT_OOB_CAP));
     }
     p.oob = c->d_oob;
     p.oob_count = c->d_oob_count;
@@ -852,19 +770,15 @@ static int render_launch(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
   // lists' order uses them)
   if (p.tile_order) {
     const size_t items = 4 * (size_t)p.ntiles_local;
-    if (items > c->item_cost_cap) {
-      (void)hipFree(c->d_item_cost);
-      c->d_item_cost = nullptr;
-      c->item_cost_cap = 0;
+    if (!c->d_item_cost.holds(items)) {
       c->cost_hist.valid = 0;
-      HIP_TRY(hipMalloc((void**)&c->d_item_cost, items * sizeof(uint32_t)));
-      c->item_cost_cap = items;
+      HIP_TRY(c->d_item_cost.grow(items, items));
     }
     p.item_cost = c->d_item_cost;
     p.cost_sum = cost_sum_of(c);
   }
   if (!c->d_frame_check) {
-    HIP_TRY(hipMalloc((void**)&c->d_frame_check, 4 * sizeof(unsigned long long)));
+    HIP_TRY(c->d_frame_check.alloc(4));
     HIP_TRY(hipMemsetAsync(c->d_frame_check, 0, 4 * sizeof(unsigned long long), s));
   }
   p.frame_check = c->d_frame_check;
@@ -930,7 +844,7 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
     if (actr[7]) {  // never expected (the same frame's lists): reported, and the next build reads back
       lists_changed(c);
       return rt_set_error(RT_EHITBUF, "%u candidate-list entries, %u expected: render again", actr[6],
-                          c->known.total);
+                          c->forecast.known.total);
     }
   }
   for (int k = 0; k < RT_NSTATS; k++) {  // the copies of each counter (RT_STAT_SETS)
@@ -972,10 +886,10 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   out->cand_prims = c->cand_prims;
   out->cand_entries = c->cand_entries;
   out->cand_global = c->cand_global;
-  if (need > c->hit_cap) {  // the frame is incomplete: grow for the next render
+  if (need > c->hit_cap()) {  // the frame is incomplete: grow for the next render
     c->hit_need = need + need / 4 + 1024;
     return rt_set_error(RT_EHITBUF, "%llu hit records, %zu per region held (grown to %zu: render again)",
-                        records, c->hit_cap, c->hit_need);
+                        records, c->hit_cap(), c->hit_need);
   }
   if (out->depth_overflow)
     return rt_set_error(RT_EDEPTH, "%llu paths overflowed the bounce limit or a traversal stack",
@@ -1037,12 +951,9 @@ extern "C" int rt_hip_render_image(rt_hip_ctx* c, const rt_frame* f, float* h_rg
   HIP_TRY(hipSetDevice(c->device));
   size_t nt = rt_hip_tile_buffer_floats(f->width, f->height, 1);
   size_t npx = (size_t)f->width * f->height;
-  float *d_tiles = nullptr, *d_rgb = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_tiles, nt * sizeof(float)));
-  if (hipMalloc((void**)&d_rgb, npx * 3 * sizeof(float)) != hipSuccess) {
-    (void)hipFree(d_tiles);
-    return rt_set_error(RT_EHIP, "hipMalloc image");
-  }
+  DevBuf<float> d_tiles, d_rgb;
+  HIP_TRY(d_tiles.alloc(nt));
+  if (d_rgb.alloc(npx * 3) != hipSuccess) return rt_set_error(RT_EHIP, "hipMalloc image");
   rt_stats tmp;
   int rc = RT_OK;
   for (int attempt = 0; attempt < 3; attempt++) {  // again after the hit or list buffers grew
@@ -1054,8 +965,6 @@ extern "C" int rt_hip_render_image(rt_hip_ctx* c, const rt_frame* f, float* h_rg
     if (!rc) rc = rt_hip_stats(c, st ? st : &tmp);
     if (rc != RT_EHITBUF) break;
   }
-  (void)hipFree(d_tiles);
-  (void)hipFree(d_rgb);
   return rc;
 }
 
@@ -1118,19 +1027,16 @@ extern "C" int rt_hip_render_image_gbuffer(rt_hip_ctx* c, const rt_frame* f, flo
   const size_t ng = rt_hip_gbuffer_tile_words(f->width, f->height, 1);
   const size_t npx = (size_t)f->width * f->height;
   const size_t nsw = npx * 4 * RT_GB_WORDS;
-  float *d_tiles = nullptr, *d_rgb = nullptr;
-  uint32_t *d_gt = nullptr, *d_gs = nullptr;
+  DevBuf<float> d_tiles, d_rgb;
+  DevBuf<uint32_t> d_gt, d_gs;
+  if (d_tiles.alloc(nt) != hipSuccess || d_rgb.alloc(npx * 3) != hipSuccess || d_gt.alloc(ng) != hipSuccess ||
+      d_gs.alloc(nsw) != hipSuccess)
+    return rt_set_error(RT_EHIP, "hipMalloc image and G-buffer");
   int rc = RT_OK;
-  if (hipMalloc((void**)&d_tiles, nt * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&d_rgb, npx * 3 * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&d_gt, ng * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&d_gs, nsw * sizeof(uint32_t)) != hipSuccess)
-    rc = rt_set_error(RT_EHIP, "hipMalloc image and G-buffer");
   const int was = c->gbuffer;
   c->gbuffer = 1;
   rt_stats tmp;
-  const bool have = rc == RT_OK;
-  for (int attempt = 0; have && attempt < 3; attempt++) {  // again after the hit or list buffers grew
+  for (int attempt = 0; attempt < 3; attempt++) {  // again after the hit or list buffers grew
     rc = rt_hip_render(c, f, 0, 1, d_tiles, nullptr);
     if (!rc) rc = rt_hip_assemble(c, f, d_tiles, 1, d_rgb, nullptr);
     if (!rc) rc = rt_hip_gbuffer(c, f, 0, 1, d_gt, nullptr);
@@ -1145,10 +1051,6 @@ extern "C" int rt_hip_render_image_gbuffer(rt_hip_ctx* c, const rt_frame* f, flo
   }
   c->gbuffer = was;
   if (!was) c->gb_valid = 0;
-  (void)hipFree(d_tiles);
-  (void)hipFree(d_rgb);
-  (void)hipFree(d_gt);
-  (void)hipFree(d_gs);
   return rc;
 }
 
@@ -1172,12 +1074,9 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   int rc = rt_frame_from_camera_any(&big, &f);
   if (rc) return rc;
   const size_t nhi = (size_t)big.width * big.height, nlo = (size_t)cam->width * cam->height;
-  uint32_t *d_hi = nullptr, *d_lo = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_hi, nhi * sizeof(uint32_t)));
-  if (hipMalloc((void**)&d_lo, nlo * sizeof(uint32_t)) != hipSuccess) {
-    (void)hipFree(d_hi);
-    return rt_set_error(RT_EHIP, "hipMalloc image");
-  }
+  DevBuf<uint32_t> d_hi, d_lo;
+  HIP_TRY(d_hi.alloc(nhi));
+  if (d_lo.alloc(nlo) != hipSuccess) return rt_set_error(RT_EHIP, "hipMalloc image");
   hipStream_t s = c->stream;
   KParams p = scene_params(c);
   p.u = rt::f3{f.u.x, f.u.y, f.u.z};
@@ -1190,16 +1089,12 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   p.ntiles_total = tiles_x_of(big.width) * tiles_y_of(big.height);
   p.nranks = 1;
   p.ntiles_local = p.ntiles_total;
-  p.out = (float*)d_hi;
+  p.out = (float*)d_hi.get();
   p.tile_counter = c->d_counter;
   p.stats = c->d_stats;
   const int accel = (c->accel == RT_ACCEL_FLAT || !c->d_node) ? RT_ACCEL_FLAT_D : RT_ACCEL_OCTREE_D;
   rc = shadow_prepare(c, s);
-  if (rc) {
-    (void)hipFree(d_hi);
-    (void)hipFree(d_lo);
-    return rc;
-  }
+  if (rc) return rc;
   if (c->exact_shadows) {
     p.node_mu = c->d_node_mu;
     p.sh_global = c->d_sh_global;
@@ -1212,11 +1107,7 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   c->d_cand_valid = nullptr;
   if (c->accel == RT_ACCEL_OCTREE && c->d_node && c->exact_camera) {
     rc = cand_prepare(c, &f, &p, s, 1);
-    if (rc) {
-      (void)hipFree(d_hi);
-      (void)hipFree(d_lo);
-      return rc;
-    }
+    if (rc) return rc;
   }
   c->cost_hist.valid = 0;  // the counters are the compat render's
   if (hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s) != hipSuccess ||
@@ -1228,8 +1119,6 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   rt_stats tmp;
   if (!rc) rc = rt_hip_stats(c, st ? st : &tmp);
   if (st) st->camera = st->pixels;  // one camera ray per high-resolution pixel
-  (void)hipFree(d_hi);
-  (void)hipFree(d_lo);
   return rc;
 }
 

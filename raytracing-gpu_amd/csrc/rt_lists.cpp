@@ -185,19 +185,8 @@ extern "C" int rt_hip_cand_tile_entries(rt_hip_ctx* c, unsigned int* out, size_t
 // launches: count -> scan -> (one small read-back for the list sizes) ->
 // fill.  Everything is derived from the frame in double, rounded so that
 // each bound stays conservative.
-template <class T>
-static int grow_dev(T** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return RT_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  // headroom past a new camera's estimate (the last build's size + 1/4 +
-  // 4096, cand_prepare): growing a buffer frees the old one, and hipFree
-  // waits for the device -- a whole frame's host lead lost mid-build
-  size_t n = need + need / 2 + 8192;
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
-  return RT_OK;
-}
+// the headroom of the lists' entry and offset buffers (rt_mem.h half_more)
+static size_t list_room(size_t need) { return half_more(need, 8192); }
 
 static double d3dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
@@ -223,7 +212,7 @@ extern "C" int rt_hip_set_cand_item_cap(rt_hip_ctx* c, unsigned cap) {
 
 // the trace's item-clock sum in the frame counters (KParams::cost_sum)
 unsigned long long* cost_sum_of(rt_hip_ctx* c) {
-  return (unsigned long long*)((char*)c->d_counter + kItemCounterBytes + kStatBytes + kHitCounterBytes);
+  return (unsigned long long*)((char*)c->d_counter.get() + kItemCounterBytes + kStatBytes + kHitCounterBytes);
 }
 
 // Frame constants of the candidate lists for rank/nranks (no device work).
@@ -350,19 +339,6 @@ int cand_params(const rt_frame* f, const float scene_c[3], float scene_r, float 
   return RT_OK;
 }
 
-static int ensure_tmp(rt_hip_ctx* c, size_t bytes) {
-  // never null once ensured: rt_cand_scan takes a null temp for a size query,
-  // also on its one-workgroup path, which needs none
-  if (bytes < 256) bytes = 256;
-  if (bytes <= c->scan_tmp_bytes && c->d_scan_tmp) return RT_OK;
-  (void)hipFree(c->d_scan_tmp);
-  c->d_scan_tmp = nullptr;
-  bytes += bytes / 2 + 65536;  // headroom (as grow_dev): a new camera's sort is a little longer
-  HIP_TRY(hipMalloc(&c->d_scan_tmp, bytes));
-  c->scan_tmp_bytes = bytes;
-  return RT_OK;
-}
-
 // The last render's kept-entry count (rt_hip_stats reads it) outlives a list
 // build that overwrites the offsets it points into: saved in stream order to
 // a word no build writes (d_cand_ctr[8]).
@@ -373,43 +349,28 @@ static int save_valid(rt_hip_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
-// The entry buffers (keys, vals, keys2, cand) for n entries.
+// The entry buffers (keys, vals, keys2, cand) for n entries: all four or
+// none (a failure leaves the later ones empty, so the next call starts over).
 static int cand_entry_buffers(rt_hip_ctx* c, size_t n) {
-  if (n + 1 <= c->cand_cap) return RT_OK;
+  DevBuf<uint32_t>* const all[] = {&c->d_cand_keys, &c->d_cand_vals, &c->d_cand_keys2, &c->d_cand};
+  if (std::all_of(std::begin(all), std::end(all), [&](const DevBuf<uint32_t>* b) { return b->holds(n + 1); }))
+    return RT_OK;
   c->ext_ready = 0;  // consumed lists (ext) point into these
-  for (uint32_t** b : {&c->d_cand_keys, &c->d_cand_vals, &c->d_cand_keys2, &c->d_cand}) {
-    (void)hipFree(*b);
-    *b = nullptr;
-  }
-  c->cand_cap = 0;  // set only once all four entry buffers exist
-  size_t cap = 0;
-  int rc = grow_dev(&c->d_cand_keys, &cap, n + 1);
-  if (rc) return rc;
-  for (uint32_t** b : {&c->d_cand_vals, &c->d_cand_keys2, &c->d_cand})
-    HIP_TRY(hipMalloc((void**)b, cap * sizeof(uint32_t)));
-  c->cand_cap = cap;
+  for (DevBuf<uint32_t>* b : all) b->reset();
+  HIP_TRY(c->d_cand_keys.grow(n + 1, list_room(n + 1)));
+  for (DevBuf<uint32_t>* b : {&c->d_cand_vals, &c->d_cand_keys2, &c->d_cand})
+    HIP_TRY(b->alloc(c->d_cand_keys.cap()));
   return RT_OK;
 }
 
 // The per-tile offsets and work-order buffers for nt tiles.
 static int cand_tile_buffers(rt_hip_ctx* c, size_t nt) {
-  if (nt + 1 > c->cand_tiles_cap || nt + 1 > c->order_cap) {
+  if (!c->d_cand_start.holds(nt + 1) || !c->d_order.holds(3 * (nt + 1))) {
     c->ext_ready = 0;  // the consumed lists' offsets and work order live here
     if (c->d_cand_valid && c->d_cand_valid != c->d_cand_ctr + 8) c->d_cand_valid = nullptr;
   }
-  if (nt + 1 > c->cand_tiles_cap) {
-    size_t cap = c->cand_tiles_cap;
-    int rc = grow_dev(&c->d_cand_start, &cap, nt + 1);
-    if (rc) return rc;
-    c->cand_tiles_cap = cap;
-  }
-  if (nt + 1 > c->order_cap) {
-    (void)hipFree(c->d_order);
-    c->d_order = nullptr;
-    c->order_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->d_order, 3 * (nt + 1) * sizeof(uint32_t)));
-    c->order_cap = nt + 1;
-  }
+  HIP_TRY(c->d_cand_start.grow(nt + 1, list_room(nt + 1)));
+  HIP_TRY(c->d_order.grow(3 * (nt + 1), 3 * (nt + 1)));
   return RT_OK;
 }
 
@@ -417,22 +378,19 @@ static int cand_tile_buffers(rt_hip_ctx* c, size_t nt) {
 // lists' kernel parameters common to both builds.
 static int cand_order(rt_hip_ctx* c, KParams* kp, size_t nt, uint32_t total, hipStream_t s, const rt_frame* f,
                       int rank, int nranks) {
-  size_t tb = 0;
   // the item clocks of this frame's last trace on this context (its counters
   // are zeroed only by the render that follows this order)
   // -- or of the last frame of the same size and rank split: a new camera
   // (an animation's next frame) moves the costly tiles little, and the order
   // is a schedule only (any order renders the same image)
-  const bool hist = c->cost_hist.same_grid(f, rank, nranks) && c->d_item_cost && c->item_cost_cap >= 4 * nt;
+  const bool hist = c->cost_hist.same_grid(f, rank, nranks) && c->d_item_cost.holds(4 * nt);
   const uint32_t* ic = hist ? c->d_item_cost : nullptr;
   const unsigned long long* cs = hist ? cost_sum_of(c) : nullptr;
-  HIP_TRY(rt_cand_order(c->d_cand_start, (uint32_t)nt, total, c->d_order, c->d_order + nt + 1,
-                        c->d_order + 2 * (nt + 1), ic, cs, c->cost_waves, nullptr, &tb, s));
-  int rc = ensure_tmp(c, tb);
-  if (rc) return rc;
-  tb = c->scan_tmp_bytes;
-  HIP_TRY(rt_cand_order(c->d_cand_start, (uint32_t)nt, total, c->d_order, c->d_order + nt + 1,
-                        c->d_order + 2 * (nt + 1), ic, cs, c->cost_waves, c->d_scan_tmp, &tb, s));
+  const auto order = [&](void* tmp, size_t* tb) {
+    return rt_cand_order(c->d_cand_start, (uint32_t)nt, total, c->d_order, c->d_order + nt + 1,
+                         c->d_order + 2 * (nt + 1), ic, cs, c->cost_waves, tmp, tb, s);
+  };
+  HIP_TRY(with_tmp(c->d_scan_tmp, order));
   kp->tile_order = c->d_order + 2 * (nt + 1);
   kp->n_heavy = c->d_order + (nt + 1) + nt;  // the scan of the heavy flags: its total
   kp->cand_start = c->d_cand_start;
@@ -468,6 +426,20 @@ static uint32_t cand_chunk_shift(uint32_t split) {
   return sh;
 }
 
+// The buffers every build of a scene uses, with their sizes: fn(buffer, n)
+// for each until one returns false.  They exist together: a partial set left
+// by a failure is freed, never allocated over.
+template <class Fn>
+static bool cand_scene_buffers(rt_hip_ctx* c, Fn&& fn) {
+  const size_t np1 = (size_t)c->nprim + 1, nw = (size_t)rt_cand_big_waves() + 1;
+  return fn(c->d_cand_list, np1) && fn(c->d_cand_fp, np1 * rt_cand_footprint_bytes()) &&
+         fn(c->d_cand_sfp, 2 * np1) && fn(c->d_cand_visits, np1) && fn(c->d_cand_off, np1) &&
+         fn(c->d_cand_global, np1) && fn(c->d_cand_big, np1) && fn(c->d_cand_ctr, 32) &&
+         fn(c->d_cand_skip, np1) && fn(c->d_cand_big_lane, (size_t)kBigLaneCap * 64) &&
+         fn(c->d_cand_items, (size_t)kItemCap + 1) && fn(c->d_cand_wave_items, nw) &&
+         fn(c->d_cand_wave_base, nw) && fn(c->d_scan_bsum, (size_t)rt_cand_scan_dev_tiles(c->nprim));
+}
+
 static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glob_copies, uint32_t* total_out,
                       uint32_t* nglobal_out, const ListShape* known = nullptr, ListShape* shape = nullptr) {
   int rc = RT_OK;
@@ -482,44 +454,22 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   cp.nprim = c->nprim;
   const size_t np = c->nprim;
   if (!c->d_prim_leaf && c->d_node) {  // once per scene: which leaf holds each prim
-    HIP_TRY(hipMalloc((void**)&c->d_prim_leaf, (np + 1) * sizeof(uint32_t)));
+    HIP_TRY(c->d_prim_leaf.alloc(np + 1));
     HIP_TRY(hipMemsetAsync(c->d_prim_leaf, 0xff, (np + 1) * sizeof(uint32_t), s));  // atomicMin's start
     HIP_TRY(rt_cand_prim_leaf(c->d_node, (uint32_t)c->info.nodes, c->d_tri, c->d_prim_leaf, s));
   }
   cp.node = c->d_node;
   cp.prim_leaf = c->d_prim_leaf;
-  if (!c->h_cand) {
-    // h_cand is allocated last: a partial set left by an earlier failure is
-    // freed here, never allocated over
-    for (void** b : {(void**)&c->d_cand_list, &c->d_cand_fp, (void**)&c->d_cand_sfp, (void**)&c->d_cand_visits,
-                     (void**)&c->d_cand_off,
-                     (void**)&c->d_cand_global, (void**)&c->d_cand_big, (void**)&c->d_cand_ctr,
-                     (void**)&c->d_cand_skip, (void**)&c->d_cand_big_lane, (void**)&c->d_cand_items,
-                     (void**)&c->d_cand_wave_items, (void**)&c->d_cand_wave_base, (void**)&c->d_scan_bsum}) {
-      (void)hipFree(*b);
-      *b = nullptr;
-    }
-    HIP_TRY(hipMalloc((void**)&c->d_cand_list, (np + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&c->d_cand_fp, (np + 1) * rt_cand_footprint_bytes()));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_sfp, 2 * (np + 1) * sizeof(uint4)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_visits, (np + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_off, (np + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_global, (np + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_big, (np + 1) * sizeof(uint32_t)));
-    // [8]: a saved valid count; [16..23]: the last asynchronous build's ctr[0..7]
-    HIP_TRY(hipMalloc((void**)&c->d_cand_ctr, 32 * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_skip, (np + 1) * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_big_lane, (size_t)kBigLaneCap * 64 * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_cand_items, ((size_t)kItemCap + 1) * sizeof(uint2)));
-    const size_t nw = (size_t)rt_cand_big_waves() + 1;
-    HIP_TRY(hipMalloc((void**)&c->d_cand_wave_items, nw * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(c->d_cand_wave_items, 0, nw * sizeof(uint32_t)));  // [last] stays 0
-    HIP_TRY(hipMalloc((void**)&c->d_cand_wave_base, nw * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&c->d_scan_bsum, (size_t)rt_cand_scan_dev_tiles((uint32_t)np) * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void**)&c->h_cand, 8 * sizeof(uint32_t), hipHostMallocDefault));
+  if (!cand_scene_buffers(c, [](auto& b, size_t n) { return b.holds(n); }) || !c->h_cand.holds(8)) {
+    cand_scene_buffers(c, [](auto& b, size_t) { return b.reset(), true; });
+    hipError_t he = hipSuccess;
+    cand_scene_buffers(c, [&](auto& b, size_t n) { return (he = b.alloc(n)) == hipSuccess; });
+    HIP_TRY(he);
+    HIP_TRY(hipMemset(c->d_cand_wave_items, 0, c->d_cand_wave_items.cap() * sizeof(uint32_t)));  // [last] stays 0
+    HIP_TRY(c->h_cand.grow(8, 8));
   }
   cp.list = c->d_cand_list;
-  cp.fp = (rtc::Footprint*)c->d_cand_fp;
+  cp.fp = (rtc::Footprint*)c->d_cand_fp.get();
   // compact small footprints while tile columns fit their 16-bit intervals
   cp.sfp = cp.tiles_x < 32767 ? c->d_cand_sfp : nullptr;
   cp.store_fp = (c->cand_store_fp || !cp.sfp) ? 1u : 0u;
@@ -539,14 +489,15 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   cp.refine = c->cand_refine ? 1u : 0u;
   cp.drop_key = (uint32_t)cp.ntiles_local;  // sorts after the tiles (their keys are < ntiles_local)
   // (ctr[0 .. 7] and visits[np] are zeroed by quick_kernel)
-  size_t tb = 0;
-  HIP_TRY(rt_cand_scan(c->d_cand_visits, c->d_cand_off, (uint32_t)np, nullptr, &tb, s));
-  rc = ensure_tmp(c, tb);
-  if (rc) return rc;
-  tb = 0;
-  HIP_TRY(rt_cand_scan(c->d_cand_wave_items, c->d_cand_wave_base, rt_cand_big_waves(), nullptr, &tb, s));
-  rc = ensure_tmp(c, tb);
-  if (rc) return rc;
+  // (temporary storage for both scans, before the launches)
+  const auto prim_scan = [&](void* tmp, size_t* tb) {
+    return rt_cand_scan(c->d_cand_visits, c->d_cand_off, (uint32_t)np, tmp, tb, s);
+  };
+  HIP_TRY(with_tmp(c->d_scan_tmp, prim_scan, false));
+  const auto wave_scan = [&](void* tmp, size_t* tb) {
+    return rt_cand_scan(c->d_cand_wave_items, c->d_cand_wave_base, rt_cand_big_waves(), tmp, tb, s);
+  };
+  HIP_TRY(with_tmp(c->d_scan_tmp, wave_scan, false));
   // pass 0: flags -> compact list of the prims the float fast path leaves
   // (over this build's slice of the prims only)
   if (cp.prim1 > cp.nprim || cp.prim0 > cp.prim1) return rt_set_error(RT_EINVAL, "prim slice");
@@ -556,8 +507,8 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   HIP_TRY(rt_cand_count(&cp, s));
   HIP_TRY(rt_cand_big_count(&cp, s));
   // the big footprints' emission items (a scan over the big_count waves)
-  tb = c->scan_tmp_bytes;
-  HIP_TRY(rt_cand_scan(c->d_cand_wave_items, c->d_cand_wave_base, rt_cand_big_waves(), c->d_scan_tmp, &tb, s));
+  size_t tb = c->d_scan_tmp.cap();
+  HIP_TRY(wave_scan(c->d_scan_tmp, &tb));
   HIP_TRY(rt_cand_items(&cp, s));
   // over the list's length only (ctr[3], on the device); the entry total -> ctr[6]
   HIP_TRY(rt_cand_scan_dev(c->d_cand_visits, c->d_cand_off, (uint32_t)np, c->d_cand_ctr + 3, c->d_cand_ctr + 6,
@@ -606,13 +557,7 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
     HIP_TRY(rt_cand_big(&cp, nbig, s));
   else
     HIP_TRY(rt_cand_big_items(&cp, nitems, 0, s));
-  if (shape) {
-    shape->total = total;
-    shape->nglobal = nglobal;
-    shape->nbig = nbig;
-    shape->nitems = nitems;
-    shape->over = items_over;
-  }
+  if (shape) shape->set_sizes(c->h_cand);
   *total_out = total;
   *nglobal_out = nglobal;
   return RT_OK;
@@ -624,12 +569,10 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
 static int cand_sort(rt_hip_ctx* c, uint32_t* keys, uint32_t* keys2, uint32_t* vals, uint32_t* vals2, uint32_t n,
                      size_t n_keys, hipStream_t s, int begin_bit = 0) {
   const int bits = key_bits(n_keys);
-  size_t tb = 0;
-  HIP_TRY(rt_cand_sort(keys, keys2, vals, vals2, n, begin_bit, bits, nullptr, &tb, s));
-  int rc = ensure_tmp(c, tb);
-  if (rc) return rc;
-  tb = c->scan_tmp_bytes;
-  if (n) HIP_TRY(rt_cand_sort(keys, keys2, vals, vals2, n, begin_bit, bits, c->d_scan_tmp, &tb, s));
+  const auto sort = [&](void* tmp, size_t* tb) {
+    return rt_cand_sort(keys, keys2, vals, vals2, n, begin_bit, bits, tmp, tb, s);
+  };
+  HIP_TRY(with_tmp(c->d_scan_tmp, sort, n != 0));
   return RT_OK;
 }
 
@@ -645,125 +588,55 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   cp.prim1 = c->nprim;
   const size_t nt = (size_t)kp->ntiles_local;
   uint32_t total = 0, nglobal = 0;
-  // The last build's counters, read back without waiting after an
-  // estimated-shape build below: the next estimate starts from them
-  if (c->snap_pending && c->ev_kept && hipEventQuery(c->ev_kept) == hipSuccess) {
-    const uint32_t* h = c->h_kept + 1;  // ctr[0..7]
-    if (h[7]) {  // that frame outgrew its estimate (reported): the next build reads back
-      c->known.valid = c->kept_for.valid = 0;
-      c->kept_pending = 0;
-    } else if (c->known.valid) {
-      // the counters are those of the frame the snapshot was taken for
-      // (kept_pend: set with snap_pending, below), not of the read-back frame
-      // known still names: that one rendered again must not match them as its
-      // own exact shape -- it is one more new camera, sized with headroom
-      c->known.set(&c->kept_pend.frame, c->kept_pend.rank, c->kept_pend.nranks);
-      c->known.total = h[6];
-      c->known.nglobal = h[1];
-      c->known.nbig = h[2];
-      c->known.nitems = h[4];
-      c->known.over = h[5];
-    }
-    c->snap_pending = 0;
-  }
-  // Asynchronous (no host wait) for a frame whose lists were built before
-  // with a read-back -- its sizes are deterministic -- and, with headroom,
-  // for a new camera of the same size and rank split (an animation's next
-  // frame, a panned view): the last build's sizes + 1/4 size the buffers and
-  // launches, every kernel checks its counts on the device, and a frame past
-  // them is reported (RT_EHITBUF via ctr[7], rt_hip_stats / the frame check)
-  // and built again with a read-back.  The first frame of a size or split,
-  // the compatibility mode and cand_verify's rebuild (every footprint kept)
-  // read their sizes back.
-  const bool exact_shape = c->known.same(f, kp->rank, kp->nranks);
-  const bool est_shape = !exact_shape && c->known.same_grid(f, kp->rank, kp->nranks);
-  const bool async = c->async_lists && !c->cand_store_fp && !compat && (exact_shape || est_shape);
-  ListShape est = c->known;
-  if (est_shape) {
-    est.total = c->known.total + c->known.total / 4 + 4096;
-    est.nglobal = c->known.nglobal + c->known.nglobal / 4 + 64;
-    est.nbig = c->known.nbig + c->known.nbig / 4 + 64;
-    est.nitems = c->known.nitems + c->known.nitems / 4 + 64;
-  }
-  rc = cand_build(c, cp, s, 0, &total, &nglobal, async ? &est : nullptr, async ? nullptr : &c->known);
+  ListForecast& fc = c->forecast;
+  const int rank = kp->rank, nranks = kp->nranks;
+  // the last estimated-shape build's counters, once their read-back is done
+  const auto arrived = [&] { return c->ev_kept && hipEventQuery(c->ev_kept) == hipSuccess; };
+  if (fc.snap_pending && arrived()) fc.absorb_snapshot(c->h_kept + 1);
+  const ListPlan plan = fc.plan(f, rank, nranks, c->async_lists, c->cand_store_fp, compat);
+  const bool async = plan.async;
+  ListShape built;
+  rc = cand_build(c, cp, s, 0, &total, &nglobal, async ? &plan.shape : nullptr, async ? nullptr : &built);
   if (rc) return rc;
   c->last_async = async ? 1 : 0;
-  if (async) nglobal = 0;  // on the device (ctr[1])
-  if (!async && !compat) {  // the sizes just read back size this frame's later builds
-    c->known.set(f, kp->rank, kp->nranks);
-  } else if (!async) {
-    c->known.valid = 0;
-  }
+  if (async)
+    nglobal = 0;  // on the device (ctr[1])
+  else
+    fc.record_build(built, f, rank, nranks, compat);
   rc = cand_tile_buffers(c, nt);
   if (rc) return rc;
   // the kept count of the last build of this size and split, once its
   // read-back is done
-  if (c->kept_pending && c->ev_kept && hipEventQuery(c->ev_kept) == hipSuccess) {
-    c->kept = *c->h_kept;
-    c->kept_for = c->kept_pend;
-    c->kept_ready = 1;
-    c->kept_pending = 0;
-  }
-  // the kept entries compacted before the sort (the refinement drops ~55 %
-  // of them on C5): an asynchronous build takes the kept count of the same
-  // frame's earlier build; a fresh frame (a new camera: the build read its
-  // total back anyway) reads its own back after the compaction's scan -- one
-  // more short host wait instead of sorting the dropped entries (sorting them
-  // all measured lists 1.96 vs 1.83 / 1.85 ms on C5, profiles/r08_compact/)
-  // (for a new camera the last frame's kept count + 1/16: the scatter writes
-  // the unused tail as dropped, and a count past it sets ctr[7])
-  const bool kept_same = c->kept_for.same(f, kp->rank, kp->nranks);
-  const bool compact_known = async && c->cand_refine && c->kept_ready &&
-                             (kept_same || c->kept_for.same_grid(f, kp->rank, kp->nranks)) &&
-                             c->kept <= total && total > 0;
-  const bool compact_fresh = !async && !compat && !c->cand_store_fp && c->cand_refine && total > 0;
+  if (fc.kept_pending && arrived()) fc.absorb_kept(*c->h_kept);
+  const ListCompaction compact = fc.compaction(plan, f, rank, nranks, total, c->cand_refine, c->cand_store_fp, compat);
   bool kept_now = false;
-  if (compact_known || compact_fresh) {
+  if (compact) {
     // the kept entries (stable) -> keys2 / d_cand, sorted back into keys /
     // vals, and the buffer pairs swapped so that the sorted ones are where
     // the uncompacted path leaves them
     const uint32_t nw = rt_cand_part_waves(total);
-    if ((size_t)2 * nw + 4 > c->part_cap) {
-      (void)hipFree(c->d_part);
-      c->d_part = nullptr;
-      c->part_cap = 0;
-      const size_t cap = 2 * ((size_t)nw + nw / 2) + 1024;  // headroom (as grow_dev)
-      HIP_TRY(hipMalloc((void**)&c->d_part, cap * sizeof(uint32_t)));
-      c->part_cap = cap;
-    }
+    HIP_TRY(c->d_part.grow((size_t)2 * nw + 4, 2 * ((size_t)nw + nw / 2) + 1024));  // headroom (as list_room)
     uint32_t* cnt = c->d_part;
     uint32_t* off = c->d_part + nw + 1;
-    size_t tmpb = 0;
-    // (only the build's own entries, ctr[6]; fewer kept than last time --
-    // never expected -- leave a tail the scatter writes as dropped)
-    uint32_t cap = total;
-    if (compact_known) {
-      cap = kept_same ? c->kept : c->kept + c->kept / 16 + 4096;
-      if (cap > total) cap = total;
-    }
-    HIP_TRY(rt_cand_compact(c->d_cand_keys, c->d_cand_vals, total, c->d_cand_ctr + 6, (uint32_t)nt, cap, cnt, off,
-                            nullptr, &tmpb, c->d_cand_keys2, c->d_cand, c->d_cand_ctr + 7, s));
-    rc = ensure_tmp(c, tmpb);
-    if (rc) return rc;
-    tmpb = c->scan_tmp_bytes;
-    HIP_TRY(rt_cand_compact(c->d_cand_keys, c->d_cand_vals, total, c->d_cand_ctr + 6, (uint32_t)nt, cap, cnt, off,
-                            c->d_scan_tmp, &tmpb, c->d_cand_keys2, c->d_cand, c->d_cand_ctr + 7, s));
-    uint32_t kept = cap;
-    if (compact_fresh) {  // off[nw] = the kept entries
-      if (!c->h_kept) HIP_TRY(hipHostMalloc((void**)&c->h_kept, 9 * sizeof(uint32_t), hipHostMallocDefault));
+    const auto compaction = [&](void* tmp, size_t* tb) {
+      return rt_cand_compact(c->d_cand_keys, c->d_cand_vals, total, c->d_cand_ctr + 6, (uint32_t)nt, compact.cap, cnt,
+                             off, tmp, tb, c->d_cand_keys2, c->d_cand, c->d_cand_ctr + 7, s);
+    };
+    HIP_TRY(with_tmp(c->d_scan_tmp, compaction));
+    uint32_t kept = compact.cap;
+    if (compact.fresh) {  // off[nw] = the kept entries
+      HIP_TRY(c->h_kept.grow(9, 9));
       HIP_TRY(hipMemcpyAsync(c->h_kept, off + nw, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       kept = *c->h_kept;
       if (kept > total) return rt_set_error(RT_EHIP, "compaction kept %u of %u entries", kept, total);
-      c->kept = kept;
-      c->kept_ready = 1;
-      c->kept_for.set(f, kp->rank, kp->nranks);
+      fc.record_kept(kept, f, rank, nranks);
       kept_now = true;
     }
     rc = cand_sort(c, c->d_cand_keys2, c->d_cand_keys, c->d_cand, c->d_cand_vals, kept, nt + 1, s);
     if (rc) return rc;
-    std::swap(c->d_cand_keys, c->d_cand_keys2);
-    std::swap(c->d_cand_vals, c->d_cand);
+    swap(c->d_cand_keys, c->d_cand_keys2);
+    swap(c->d_cand_vals, c->d_cand);
     total = kept;
   } else {
     // an asynchronous build's entries past its own total (never expected): dropped
@@ -775,27 +648,20 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   // start[nt] = the entries with a tile (the dropped ones sort after them)
   // (an asynchronous build's counters snapshot for rt_hip_stats, where no build writes)
   HIP_TRY(rt_cand_bounds(c->d_cand_keys2, total, c->d_cand_start, (uint32_t)nt, async ? c->d_cand_ctr : nullptr, s));
-  if (c->cand_refine && !compat && !kept_now && (!kept_same || est_shape) &&
-      !(c->kept_pending && c->kept_pend.same(f, kp->rank, kp->nranks))) {
-    // this frame's kept count -- and after an estimated-shape build its
-    // counters (bounds_kernel's snapshot) -- for the later builds, read back
-    // without waiting
-    if (!c->h_kept) HIP_TRY(hipHostMalloc((void**)&c->h_kept, 9 * sizeof(uint32_t), hipHostMallocDefault));
+  if (fc.wants_late_readback(plan, f, rank, nranks, c->cand_refine, compat, kept_now)) {
+    HIP_TRY(c->h_kept.grow(9, 9));
     if (!c->ev_kept) HIP_TRY(hipEventCreateWithFlags(&c->ev_kept, hipEventDisableTiming));
     HIP_TRY(hipMemcpyAsync(c->h_kept, c->d_cand_start + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (est_shape) HIP_TRY(hipMemcpyAsync(c->h_kept + 1, c->d_cand_ctr + 16, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (plan.estimated)  // bounds_kernel's snapshot of its counters
+      HIP_TRY(hipMemcpyAsync(c->h_kept + 1, c->d_cand_ctr + 16, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(c->ev_kept, s));
-    // (the count in hand, if any, stays usable -- for this size and split --
-    // until this one arrives: the host runs frames ahead of the device)
-    c->kept_pend.set(f, kp->rank, kp->nranks);
-    c->kept_pending = 1;
-    c->snap_pending = est_shape ? 1 : 0;
+    fc.late_readback_requested(plan, f, rank, nranks);
   }
   // the sorted keys are spent: their buffer takes the per-entry skip bounds
-  float* entry_skip = (float*)c->d_cand_keys2;
+  float* entry_skip = (float*)c->d_cand_keys2.get();
   HIP_TRY(rt_cand_entry_skip(c->d_cand, c->d_cand_skip, entry_skip, total, c->d_cand_start + nt, s));
   // longest-first work order of the rank's tiles (heavy lists first)
-  rc = cand_order(c, kp, nt, total, s, f, kp->rank, kp->nranks);
+  rc = cand_order(c, kp, nt, total, s, f, rank, nranks);
   if (rc) return rc;
   kp->cand = c->d_cand;
   kp->cand_global = c->d_cand_global;
@@ -865,45 +731,20 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
   HIP_TRY(rt_cand_route_globals(c->d_cand_global, nglobal, nranks, tpr, (uint32_t)tbits, c->d_cand_keys + total,
                                 c->d_cand_vals + total, s));
   const uint32_t n = total + nglobal * (uint32_t)nranks;
-  if ((size_t)nranks + 9 > c->rstart_cap) {  // the starts, then the build's counters
-    (void)hipFree(c->d_rstart);
-    (void)hipHostFree(c->h_rstart);
-    c->d_rstart = nullptr;
-    c->h_rstart = nullptr;
-    c->rstart_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->d_rstart, ((size_t)nranks + 9) * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void**)&c->h_rstart, ((size_t)nranks + 9) * sizeof(uint32_t), hipHostMallocDefault));
-    c->rstart_cap = (size_t)nranks + 9;
-  }
-  if (3 * (size_t)n + 1 > c->send_cap) {
-    (void)hipFree(c->d_send);
-    c->d_send = nullptr;
-    c->send_cap = 0;
-    const size_t cap = 3 * ((size_t)n + n / 4 + 1024);
-    HIP_TRY(hipMalloc((void**)&c->d_send, cap * sizeof(uint32_t)));
-    c->send_cap = cap;
-  }
+  // the starts, then the build's counters
+  HIP_TRY(c->d_rstart.grow((size_t)nranks + 9, (size_t)nranks + 9));
+  HIP_TRY(c->h_rstart.grow((size_t)nranks + 9, (size_t)nranks + 9));
+  HIP_TRY(c->d_send.grow(3 * (size_t)n + 1, 3 * ((size_t)n + n / 4 + 1024)));
   // per-wave rank counts (rank-major) -> exclusive scan -> stable scatter
   const size_t nh = ((size_t)nranks + 1) * rt_cand_part_waves(n);
-  if (2 * nh + 2 > c->part_cap) {
-    (void)hipFree(c->d_part);
-    c->d_part = nullptr;
-    c->part_cap = 0;
-    const size_t cap = 2 * (nh + nh / 4) + 1024;
-    HIP_TRY(hipMalloc((void**)&c->d_part, cap * sizeof(uint32_t)));
-    c->part_cap = cap;
-  }
+  HIP_TRY(c->d_part.grow(2 * nh + 2, 2 * (nh + nh / 4) + 1024));
   uint32_t* hist = c->d_part;
   uint32_t* hoff = c->d_part + nh + 1;
   if (nh) {
-    size_t tmpb = 0;
-    HIP_TRY(rt_cand_scan(hist, hoff, (uint32_t)(nh - 1), nullptr, &tmpb, s));
-    rc = ensure_tmp(c, tmpb);
-    if (rc) return rc;
-    tmpb = c->scan_tmp_bytes;
     HIP_TRY(rt_cand_part_count(c->d_cand_keys, n, (uint32_t)tbits, nranks, hist, total, cp.tiles_x,
                                rt_blocks_x(cp.tiles_x, tb), tb, cp.drop_key, async ? c->d_cand_ctr + 6 : nullptr, s));
-    HIP_TRY(rt_cand_scan(hist, hoff, (uint32_t)(nh - 1), c->d_scan_tmp, &tmpb, s));
+    const auto scan = [&](void* tmp, size_t* bytes) { return rt_cand_scan(hist, hoff, (uint32_t)(nh - 1), tmp, bytes, s); };
+    HIP_TRY(with_tmp(c->d_scan_tmp, scan));
   }
   HIP_TRY(rt_cand_part_scatter(c->d_cand_keys, c->d_cand_vals, c->d_cand_skip, n, (uint32_t)tbits, nranks, hoff,
                                c->d_rstart, c->d_send, c->d_cand_ctr, s));
@@ -912,8 +753,7 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
                          s));
   HIP_TRY(hipStreamSynchronize(s));
   const uint32_t* hc = c->h_rstart + nranks + 1;  // ctr[0 .. 7]
-  if (async && (hc[7] || hc[6] != c->pknown.total || hc[1] != c->pknown.nglobal || hc[2] != c->pknown.nbig ||
-                hc[4] != c->pknown.nitems || hc[5] != c->pknown.over)) {
+  if (async && !c->pknown.same_sizes(hc)) {
     c->pknown.valid = 0;  // not this slice's sizes after all: build it with the read-back
     return rt_hip_cand_produce(c, f, rank, nranks, counts, nglobal_out, stream);
   }
@@ -958,14 +798,14 @@ extern "C" int rt_hip_cand_consume(rt_hip_ctx* c, const rt_frame* f, int rank, i
   const uint32_t total = (uint32_t)(n - nglobal);
   HIP_TRY(rt_cand_bounds(c->d_cand_keys2, total, c->d_cand_start, (uint32_t)nt, nullptr, s));
   // the spent unsorted keys take the skip bounds, the spent indices the prims
-  HIP_TRY(rt_cand_gather(in, c->d_cand, (uint32_t)n, c->d_cand_vals, (float*)c->d_cand_keys, s));
+  HIP_TRY(rt_cand_gather(in, c->d_cand, (uint32_t)n, c->d_cand_vals, (float*)c->d_cand_keys.get(), s));
   KParams kp;
   std::memset(&kp, 0, sizeof kp);
   rc = cand_order(c, &kp, nt, total, s, f, rank, nranks);
   if (rc) return rc;
   c->ext = kp;
   c->ext.cand = c->d_cand_vals;
-  c->ext.cand_skip = (const float*)c->d_cand_keys;
+  c->ext.cand_skip = (const float*)c->d_cand_keys.get();
   c->ext.cand_global = c->d_cand_vals + total;
   c->ext.n_cand_global = nglobal;
   c->ext_ready = 1;

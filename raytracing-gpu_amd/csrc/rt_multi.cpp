@@ -67,7 +67,7 @@ static int cand_exchange(rt_hip_ctx* const* ctx, int n, const rt_frame* f, ncclC
       (void)hipSetDevice(ctx[r]->device);
       size_t so = 0, ro = 0;
       for (int d = 0; d < n; d++) {  // what r sends to d, and receives from d
-        if (counts[r][d]) NCCL_TRY(ncclSend(ctx[r]->d_send + 3 * so, 3 * (size_t)counts[r][d], ncclUint32, d,
+        if (counts[r][d]) NCCL_TRY(ncclSend(ctx[r]->d_send.get() + 3 * so, 3 * (size_t)counts[r][d], ncclUint32, d,
                                             comms[r], ctx[r]->stream));
         if (counts[d][r]) NCCL_TRY(ncclRecv(recv[r] + 3 * ro, 3 * (size_t)counts[d][r], ncclUint32, d,
                                             comms[r], ctx[r]->stream));
@@ -92,7 +92,7 @@ static int cand_exchange(rt_hip_ctx* const* ctx, int n, const rt_frame* f, ncclC
         // on the receiver's stream, so its consume is ordered after the copy
         // (a device-to-device hipMemcpyPeer may return before it completes)
         if (counts[r][d] &&
-            hipMemcpyPeerAsync(recv[d] + 3 * ro, ctx[d]->device, ctx[r]->d_send + 3 * so, ctx[r]->device,
+            hipMemcpyPeerAsync(recv[d] + 3 * ro, ctx[d]->device, ctx[r]->d_send.get() + 3 * so, ctx[r]->device,
                                (size_t)counts[r][d] * 12, ctx[d]->stream) != hipSuccess)
           rc = rt_set_error(RT_EHIP, "exchange: %d -> %d", r, d);
         ro += counts[r][d];

@@ -212,23 +212,17 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->last_stream ? c->last_stream : c->stream;
   HIP_TRY(hipStreamSynchronize(s));
-  const size_t n = c->hit_cap * RT_HIT_REGIONS;
-  uint32_t *lit[2] = {nullptr, nullptr}, *ctr = nullptr;
-  float4* term = nullptr;
-  unsigned long long* st = nullptr;
+  const size_t hit_cap = c->hit_cap(), n = hit_cap * RT_HIT_REGIONS;
+  DevBuf<uint32_t> lit[2], ctr;
+  DevBuf<float4> term;
+  DevBuf<unsigned long long> st;
   int rc = RT_OK;
   uint32_t hc[RT_HIT_REGIONS * 32];
-  std::vector<uint32_t> la, lb;
   unsigned long long nsh = 0;
   for (uint32_t li = 0; li < c->nlight; li++) nsh += c->light_type[li] == 1 || c->light_type[li] == 2;
-  if (hipMalloc((void**)&lit[0], n * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&lit[1], n * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&term, n * sizeof(float4)) != hipSuccess ||
-      hipMalloc((void**)&ctr, RT_HIT_REGIONS * 32 * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&st, kStatBytes) != hipSuccess) {
-    rc = rt_set_error(RT_EHIP, "hipMalloc shadow verification buffers");
-    goto done;
-  }
+  if (lit[0].alloc(n) != hipSuccess || lit[1].alloc(n) != hipSuccess || term.alloc(n) != hipSuccess ||
+      ctr.alloc(RT_HIT_REGIONS * 32) != hipSuccess || st.alloc(kStatBytes / sizeof(unsigned long long)) != hipSuccess)
+    return rt_set_error(RT_EHIP, "hipMalloc shadow verification buffers");
   for (int pass = 0; pass < 2 && !rc; pass++) {
     KParams p = c->last_p;
     p.hit_term = term;
@@ -256,20 +250,17 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
       rc = rt_set_error(RT_EHIP, "shadow verification pass %d: %s", pass,
                         hipGetErrorString(hipGetLastError()));
   }
-  if (rc) goto done;
-  la.resize(n);
-  lb.resize(n);
+  if (rc) return rc;
+  std::vector<uint32_t> la(n), lb(n);
   if (hipMemcpy(la.data(), lit[0], n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(lb.data(), lit[1], n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(hc, c->d_hit_count, sizeof hc, hipMemcpyDeviceToHost) != hipSuccess) {
-    rc = rt_set_error(RT_EHIP, "shadow verification read-back");
-    goto done;
-  }
+      hipMemcpy(hc, c->d_hit_count, sizeof hc, hipMemcpyDeviceToHost) != hipSuccess)
+    return rt_set_error(RT_EHIP, "shadow verification read-back");
   std::memset(out, 0, 4 * sizeof *out);
   for (int x = 0; x < RT_HIT_REGIONS; x++) {
-    const size_t cnt = hc[32 * x] < c->hit_cap ? hc[32 * x] : c->hit_cap;
+    const size_t cnt = hc[32 * x] < hit_cap ? hc[32 * x] : hit_cap;
     for (size_t k = first; k < cnt; k += (stride ? stride : 1)) {
-      const size_t a = (size_t)x * c->hit_cap + k;
+      const size_t a = (size_t)x * hit_cap + k;
       out[0]++;
       if (la[a] != lb[a]) {
         out[2]++;
@@ -278,13 +269,7 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
     }
   }
   out[1] = out[0] * nsh;
-done:
-  (void)hipFree(lit[0]);
-  (void)hipFree(lit[1]);
-  (void)hipFree(term);
-  (void)hipFree(ctr);
-  (void)hipFree(st);
-  return rc;
+  return RT_OK;
 }
 
 // Shadow-query probe (tests, tools): light `light`'s shadow ray from each
@@ -312,34 +297,26 @@ extern "C" int rt_hip_probe_closest(rt_hip_ctx* c, const float* origins, const f
       for (int g : b2) gmax = g > gmax ? g : gmax;
   if (gmax < c->grid) gmax = c->grid;
   const size_t chunk = (size_t)gmax * 64;
-  float *d_o = nullptr, *d_d = nullptr;
-  uint32_t* d_h = nullptr;
+  DevBuf<float> d_o, d_d;
+  DevBuf<uint32_t> d_h;
   const size_t m = n < chunk ? n : chunk;
   std::vector<uint32_t> h(2 * m + 2);
-  int rc = RT_OK;
-  if (hipMalloc((void**)&d_o, (m * 3 + 1) * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&d_d, (m * 3 + 1) * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&d_h, (2 * m + 2) * sizeof(uint32_t)) != hipSuccess)
-    rc = rt_set_error(RT_EHIP, "hipMalloc probe buffers");
-  for (size_t at = 0; rc == RT_OK && at < n; at += chunk) {  // the walk's spill area holds `chunk` rays
+  if (d_o.alloc(m * 3 + 1) != hipSuccess || d_d.alloc(m * 3 + 1) != hipSuccess || d_h.alloc(2 * m + 2) != hipSuccess)
+    return rt_set_error(RT_EHIP, "hipMalloc probe buffers");
+  for (size_t at = 0; at < n; at += chunk) {  // the walk's spill area holds `chunk` rays
     const size_t k = n - at < chunk ? n - at : chunk;
     if (hipMemcpy(d_o, origins + 3 * at, k * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_d, dirs + 3 * at, k * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         rt_launch_probe_closest(&p, d_o, d_d, (uint32_t)k, c->nprim, brute, d_h, gmax, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess ||
-        hipMemcpy(h.data(), d_h, 2 * k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = rt_set_error(RT_EHIP, "closest probe: %s", hipGetErrorString(hipGetLastError()));
-      break;
-    }
+        hipMemcpy(h.data(), d_h, 2 * k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+      return rt_set_error(RT_EHIP, "closest probe: %s", hipGetErrorString(hipGetLastError()));
     for (size_t i = 0; i < k; i++) {
       prim[at + i] = h[2 * i];
       std::memcpy(&dist[at + i], &h[2 * i + 1], sizeof(float));
     }
   }
-  (void)hipFree(d_o);
-  (void)hipFree(d_d);
-  (void)hipFree(d_h);
-  return rc;
+  return RT_OK;
 }
 
 extern "C" int rt_hip_probe_shadows(rt_hip_ctx* c, unsigned light, const float* origins, size_t n, int brute,
@@ -358,24 +335,18 @@ extern "C" int rt_hip_probe_shadows(rt_hip_ctx* c, unsigned light, const float* 
   if (!c->d_tri_prim) return rt_set_error(RT_EINVAL, "no triangles");
   KParams p = scene_params(c);
   p.lbuf = brute ? nullptr : c->d_lbuf;
-  float* d_o = nullptr;
-  uint32_t* d_h = nullptr;
+  DevBuf<float> d_o;
+  DevBuf<uint32_t> d_h;
   std::vector<uint32_t> h(n);
-  int rc = RT_OK;
-  if (hipMalloc((void**)&d_o, (n * 3 + 1) * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&d_h, (n + 1) * sizeof(uint32_t)) != hipSuccess) {
-    rc = rt_set_error(RT_EHIP, "hipMalloc probe buffers");
-  } else if (hipMemcpy(d_o, origins, n * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-             rt_launch_probe_shadow(&p, d_o, (uint32_t)n, light, (uint32_t)c->nprim, brute, d_h, s) != hipSuccess ||
-             hipStreamSynchronize(s) != hipSuccess ||
-             hipMemcpy(h.data(), d_h, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
-    rc = rt_set_error(RT_EHIP, "shadow probe: %s", hipGetErrorString(hipGetLastError()));
-  } else {
-    for (size_t i = 0; i < n; i++) hit[i] = (unsigned char)h[i];
-  }
-  (void)hipFree(d_o);
-  (void)hipFree(d_h);
-  return rc;
+  if (d_o.alloc(n * 3 + 1) != hipSuccess || d_h.alloc(n + 1) != hipSuccess)
+    return rt_set_error(RT_EHIP, "hipMalloc probe buffers");
+  if (hipMemcpy(d_o, origins, n * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      rt_launch_probe_shadow(&p, d_o, (uint32_t)n, light, (uint32_t)c->nprim, brute, d_h, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess ||
+      hipMemcpy(h.data(), d_h, n * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return rt_set_error(RT_EHIP, "shadow probe: %s", hipGetErrorString(hipGetLastError()));
+  for (size_t i = 0; i < n; i++) hit[i] = (unsigned char)h[i];
+  return RT_OK;
 }
 
 // The per-frame checks of every render since the last call (fold_kernel):

@@ -869,6 +869,62 @@ def test_async_lists_revisited_cameras(gpu, rank, nranks):
         check(k, img, st, f"far jump, render {i} (camera {k}), rank {rank}/{nranks}")
 
 
+def _tiles_and_gbuffer_of_rank(ctx, f, rank, nranks):
+    """_tiles_of_rank, plus the rank's G-buffer tile words of the same render."""
+    import ctypes as C
+    L = gpu_lib()
+    per_c = gpu_mod().tile_buffer_floats(f.width, f.height, nranks)
+    per_g = gpu_mod().gbuffer_tile_words(f.width, f.height, nranks)
+    dc, dg = C.c_void_p(), C.c_void_p()
+    assert L.rt_hip_malloc(0, per_c * 4, C.byref(dc)) == 0
+    assert L.rt_hip_malloc(0, per_g * 4, C.byref(dg)) == 0
+    try:
+        ctx.render(f, rank, nranks, dc.value)
+        ctx.gbuffer(f, rank, nranks, dg.value)
+        st = ctx.stats()
+        col, gb = np.empty(per_c, np.float32), np.empty(per_g, np.uint32)
+        assert L.rt_hip_memcpy_d2h(col.ctypes.data_as(C.c_void_p), dc, col.nbytes) == 0
+        assert L.rt_hip_memcpy_d2h(gb.ctypes.data_as(C.c_void_p), dg, gb.nbytes) == 0
+    finally:
+        L.rt_hip_free(dc)
+        L.rt_hip_free(dg)
+    n = gpu_mod().rank_tile_count(f.width, f.height, rank, nranks)
+    return col.reshape(-1, 64, 3)[:n], gb.reshape(-1, 64, 4 * gpu_mod().GB_WORDS)[:n], st
+
+
+def test_context_buffers_regrow(gpu):
+    """One context through small -> large -> a rank's share -> small -> large
+    with the G-buffer switched on late: every per-frame buffer of the context
+    (hit records, `last`, capture, the lists' entry, offset, order and
+    temporary buffers, the item clocks) takes its grow branch, and the
+    still-large buffers then serve a smaller frame.  Each step's tile buffer
+    (and G-buffer tiles) equals, bit for bit, a fresh context doing only that
+    step, with the same counts."""
+    geometry = dict(gx=4, gy=4, tris_per_sphere=1200, seed=0x5EED)
+    small = gpu.Scene.synthetic(width=64, height=36, **geometry)
+    large = gpu.Scene.synthetic(width=480, height=270, **geometry)
+    fs, fl = small.frame(), large.frame()
+    steps = [(fs, 0, 1, False), (fl, 0, 1, False), (fl, 1, 4, False), (fs, 0, 1, False), (fl, 0, 1, True)]
+
+    def run(ctx, f, rank, nranks, gbuffer):
+        if gbuffer:
+            ctx.set_gbuffer(True)
+            return _tiles_and_gbuffer_of_rank(ctx, f, rank, nranks)
+        col, st = _tiles_of_rank(ctx, f, rank, nranks)
+        return col, None, st
+
+    ctx = gpu.Context(large, "octree_gpu")
+    for i, step in enumerate(steps):
+        what = f"step {i}: {step[0].width}x{step[0].height} rank {step[1]} of {step[2]}, G-buffer {step[3]}"
+        col, gb, st = run(ctx, *step)
+        ref_col, ref_gb, ref_st = run(gpu.Context(large, "octree_gpu"), *step)
+        assert_bitexact(col, ref_col, what)
+        if gb is not None:
+            assert np.array_equal(gb, ref_gb), what + ": G-buffer tiles"
+        assert (st["closest"], st["shadow"], st["cand_entries"]) == \
+            (ref_st["closest"], ref_st["shadow"], ref_st["cand_entries"]), what
+
+
 def test_triangle_parallel_lists_two_processes(gpu):
     """Two processes (ranks of torch.distributed.run, both on GPU 0, gloo
     for the exchange since RCCL needs a device per rank): each produces its

@@ -428,6 +428,32 @@ def test_scene_lifecycle_asan(tmp_path, scene_dir):
     assert "asan scene lifecycle ok" in r.stdout
 
 
+def test_list_forecast_table(tmp_path):
+    """The list-size forecast (csrc/rt_forecast.h: which candidate-list builds
+    run without a host wait, the compaction's size, when a late read-back may
+    overwrite what is known) driven through scripted frame sequences against
+    a table derived from cand_prepare as it stood before the forecast was
+    moved out of it (tests/native/forecast_table.cpp), under the CPU
+    AddressSanitizer + UBSan build.  No GPU: the GPU tests see the forecast
+    only through images and counts, which a build that always read back
+    would pass too."""
+    import shutil
+    import subprocess
+    if not shutil.which("g++"):
+        pytest.skip("g++ missing")
+    exe = str(tmp_path / "forecast_table")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
+           "-fno-omit-frame-pointer", "-I" + os.path.join(REPO, "include"),
+           "-I" + os.path.join(REPO, "raytracing-gpu_amd", "csrc"),
+           os.path.join(REPO, "tests", "native", "forecast_table.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=60)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "list forecast table ok" in r.stdout
+
+
 def test_lightbuf_survey_host(built):
     """Host survey of the light buffers (no device): slack-grown and proven
     footprints of a small synthetic scene, both lights; the proven ones list
