@@ -246,6 +246,75 @@ int rt_hip_assemble(rt_hip_ctx *ctx, const rt_frame *frame, const float *d_gathe
  * h_rgb (W*H*3 floats, PPM order); synchronous. */
 int rt_hip_render_image(rt_hip_ctx *ctx, const rt_frame *frame, float *h_rgb, rt_stats *stats);
 
+/* Relighting (new): the last rt_hip_render's image under edited lights and
+ * materials without tracing it again.  A path's hit records (P, N, coef,
+ * object) do not depend on the lights -- trace() recurses on obj.nr * coef
+ * only (cpu/raytracer.c:19-34) and apply_light takes the hit, the object's
+ * ka/kd/ks/ns and the lights (cpu/light.c:33-100) -- and a shadow decision
+ * does not depend on a light's colour (cpu/light.c:24-31).  The context keeps
+ * the records of its last render, and per record the unshadowed-light mask
+ * of lights 0..31; a relight shades the records again, asking shadow queries
+ * only for lights whose stored decision is not current, and the result is
+ * bit for bit what a new context on the edited scene renders.
+ * rt_raytrace_multi*, the CLIs and rt_hip_render_compat do not relight.
+ *
+ * rt_hip_set_lights replaces the light table (n may differ from the old
+ * count; n = 0 is legal).  Synchronous setup, like rt_hip_set_exact_shadows:
+ * it waits for the last render's stream, uploads the table, and rebuilds the
+ * light buffer of exactly those lights whose (type, v) differs bitwise from
+ * the old light at the same index, and of new indices; unchanged lights keep
+ * their buffers, removed ones free theirs, a colour-only change builds
+ * nothing.  A build past the entry cap or out of memory makes that light's
+ * queries walk, as at rt_hip_create (rt_accel_info: lightbuf_failed,
+ * lightbuf_fail_reason); the light-buffer totals of rt_accel_info are
+ * recomputed.  Renders after it use the new table.
+ *
+ * rt_hip_set_materials takes ka, kd, ks, ns of objects[i] for every object
+ * (`triangles` is ignored); n must equal the context's object count, and nr
+ * -- all the trace reads of a material -- must equal the context's value
+ * bitwise, else RT_EINVAL and nothing changes: reflectivity changes the
+ * paths, which needs a new context.
+ *
+ * rt_hip_relight re-shades the kept records of the last rt_hip_render under
+ * the current lights and materials and folds them into d_tiles; asynchronous
+ * on `stream`.  RT_EINVAL, with nothing changed: no render yet; the last
+ * render was of another frame (compared bytewise), rank or nranks; it ran on
+ * another stream; it was rt_hip_render_compat; a non-default traversal policy
+ * is set; rt_hip_set_count_work is on.  A rank without tiles writes nothing
+ * and returns RT_OK.  A frame that overflowed its hit buffer relights what
+ * it holds and rt_hip_stats reports RT_EHITBUF again.  The G-buffer of that
+ * render stays valid (P, N and the winners do not depend on lights).  Which
+ * lights are queried: a directional or point light's stored decision is
+ * current iff its index is below 32, a shade pass of the kept records wrote
+ * it (a render with keep-visibility on, or an earlier relight) and its
+ * (type, v) has not changed since; lights from index 32 up are always
+ * queried; ambient and other lights never.  A render without
+ * keep-visibility, rt_hip_set_exact_shadows, rt_hip_set_light_buffers,
+ * rt_hip_set_lightbuf_entry_cap, rt_hip_set_cull_slack (and
+ * rt_hip_set_policy) and a reallocation of the hit buffers make every stored
+ * decision stale; colours and materials never do.
+ *
+ * rt_hip_stats after a relight: the trace-side counters (closest, camera,
+ * pixels, hits, zero_normal, depth_overflow, hit_records, cand_*) are the
+ * traced frame's, the shadow-side ones (shadow, shadow_*, shadow_zero_risk,
+ * shadow_unproven, shadow_deferred) the relight's: a relight that asked no
+ * query reads shadow == 0.  rt_hip_frame_check counts renders only.
+ *
+ * rt_hip_set_keep_visibility (default 0): with 1, renders also write the
+ * masks (4 B per record, allocated with the hit buffers), so the first relight
+ * after a render can already skip queries.  With 0 renders are exactly what
+ * they were, and the first relight of a frame allocates the buffer, asks every
+ * query and writes the masks.
+ *
+ * rt_hip_relight_image: rt_hip_relight of the whole frame (one rank, the
+ * context's stream: after rt_hip_render_image) into host memory; synchronous. */
+int rt_hip_set_lights(rt_hip_ctx *ctx, const rt_light *lights, size_t n);
+int rt_hip_set_materials(rt_hip_ctx *ctx, const rt_object *objects, size_t n);
+int rt_hip_set_keep_visibility(rt_hip_ctx *ctx, int enable);   /* default 0 */
+int rt_hip_relight(rt_hip_ctx *ctx, const rt_frame *frame, int rank, int nranks,
+                   float *d_tiles, void *stream);
+int rt_hip_relight_image(rt_hip_ctx *ctx, const rt_frame *frame, float *h_rgb, rt_stats *stats);
+
 /* Per-sample G-buffer (new; opt-in, default off): what the renderer knows
  * about each of a pixel's four camera samples beside its colour.  One record
  * of RT_GB_WORDS 32-bit words per sample, 4 per pixel in cpu sample order:

@@ -167,53 +167,55 @@ void lb_fill(LBParams& lp, const float scene_c[3], float scene_r, const float aa
   lp.proven = proven ? 1u : 0u;
 }
 
-int lbuf_prepare(rt_hip_ctx* c, hipStream_t s) {
-  if (!c->light_buffers || c->accel != RT_ACCEL_OCTREE || !c->d_node || !c->nlight) return RT_OK;
-  if (c->d_lbuf && c->lb_ulps == c->eps_ulps && c->lb_proven == c->exact_shadows) return RT_OK;
-  lbuf_release(c);
-  c->lb_dev.assign(c->nlight, nullptr);
-  c->info.lightbuf_fail_reason[0] = 0;
-  std::vector<RtLightBuf> hb(c->nlight);
-  std::memset(hb.data(), 0, hb.size() * sizeof(RtLightBuf));
+// The buffer of light li (lb_dev[li] is null, lb_host / lb_failed hold nlight
+// entries) for the context's slack and mode; a light that casts no shadow has
+// none.  RT_OK also when the build fell back to the walk (lb_failed[li]); an
+// error is a failed launch or an inconsistent build, and the caller gives
+// every buffer up.
+static int lbuf_build_one(rt_hip_ctx* c, uint32_t li, hipStream_t s) {
+  std::memset(&c->lb_host[li], 0, sizeof(RtLightBuf));
+  c->lb_failed[li] = 0;
+  const uint32_t t = c->light_type[li];
+  if (t != 1 && t != 2) return RT_OK;
   char err[256] = {0};
-  uint32_t failed = 0;
-  for (uint32_t li = 0; li < c->nlight; li++) {
-    const uint32_t t = c->light_type[li];
-    if (t != 1 && t != 2) continue;
-    LBParams lp;
-    lb_fill(lp, c->scene_c, c->scene_r, c->scene_lo, c->scene_hi, c->eps_ulps, t, &c->light_v[3 * li], c->nprim,
-            c->exact_shadows);
-    lp.tri = c->d_tri_prim;
-    lp.max_entries = c->lb_entry_cap;
-    if (const char* e = std::getenv("RT_LB_CELLS")) {  // build tuning: cells per triangle
-      const double k = std::atof(e);
-      if (k > 0.0) lp.target_cells = (uint32_t)std::fmin((double)(1u << 26), std::fmax(4096.0, lp.target_cells * k));
-    }
-    const int br = rt_lightbuf_build(&lp, &hb[li], &c->lb_dev[li], s, err, sizeof err);
-    if (br < 0) {  // not a capacity question: a failed launch or an inconsistent build
-      (void)hipGetLastError();
-      for (LBDevice*& d : c->lb_dev) {
-        rt_lightbuf_free(d);
-        d = nullptr;
-      }
-      return rt_set_error(RT_EHIP, "light buffer of light %u: %s", li, err);
-    }
-    if (br > 0) {
-      // entry or cell cap, device memory, or a zero directional vector (no
-      // grid): the light's queries walk the octree instead (hb[li] is zeroed:
-      // RT_LB_NONE), as they did before light buffers -- a scene that fits the
-      // walk still loads; in the exact-shadow mode that walk is the proven
-      // per-node multiplier walk (shadow_prepare, built by the render)
-      std::memset(&hb[li], 0, sizeof hb[li]);
-      c->lb_dev[li] = nullptr;
-      (void)hipGetLastError();  // an out-of-memory hipMalloc is not sticky; clear it anyway
-      std::snprintf(c->info.lightbuf_fail_reason, sizeof c->info.lightbuf_fail_reason, "light %u: %s", li, err);
-      failed++;
-    }
+  LBParams lp;
+  lb_fill(lp, c->scene_c, c->scene_r, c->scene_lo, c->scene_hi, c->eps_ulps, t, &c->light_v[3 * li], c->nprim,
+          c->exact_shadows);
+  lp.tri = c->d_tri_prim;
+  lp.max_entries = c->lb_entry_cap;
+  if (const char* e = std::getenv("RT_LB_CELLS")) {  // build tuning: cells per triangle
+    const double k = std::atof(e);
+    if (k > 0.0) lp.target_cells = (uint32_t)std::fmin((double)(1u << 26), std::fmax(4096.0, lp.target_cells * k));
   }
+  const int br = rt_lightbuf_build(&lp, &c->lb_host[li], &c->lb_dev[li], s, err, sizeof err);
+  if (br < 0) {  // not a capacity question: a failed launch or an inconsistent build
+    (void)hipGetLastError();
+    return rt_set_error(RT_EHIP, "light buffer of light %u: %s", li, err);
+  }
+  if (br > 0) {
+    // entry or cell cap, device memory, or a zero directional vector (no
+    // grid): the light's queries walk the octree instead (lb_host[li] is
+    // zeroed: RT_LB_NONE), as they did before light buffers -- a scene that
+    // fits the walk still loads; in the exact-shadow mode that walk is the
+    // proven per-node multiplier walk (shadow_prepare, built by the render)
+    std::memset(&c->lb_host[li], 0, sizeof(RtLightBuf));
+    c->lb_dev[li] = nullptr;
+    (void)hipGetLastError();  // an out-of-memory hipMalloc is not sticky; clear it anyway
+    std::snprintf(c->info.lightbuf_fail_reason, sizeof c->info.lightbuf_fail_reason, "light %u: %s", li, err);
+    c->lb_failed[li] = 1;
+  }
+  return RT_OK;
+}
+
+// The per-light table on the device and rt_accel_info's totals, from lb_host /
+// lb_dev / lb_failed as they stand.
+static int lbuf_publish(rt_hip_ctx* c) {
+  uint32_t failed = 0;
+  for (uint8_t f : c->lb_failed) failed += f;
   c->info.lightbuf_failed = failed;
-  HIP_TRY(c->d_lbuf.alloc(hb.size()));
-  HIP_TRY(hipMemcpy(c->d_lbuf, hb.data(), hb.size() * sizeof(RtLightBuf), hipMemcpyHostToDevice));
+  if (!failed) c->info.lightbuf_fail_reason[0] = 0;
+  if (c->d_lbuf.cap() != c->lb_host.size() || !c->d_lbuf) HIP_TRY(c->d_lbuf.alloc(c->lb_host.size()));
+  HIP_TRY(hipMemcpy(c->d_lbuf, c->lb_host.data(), c->lb_host.size() * sizeof(RtLightBuf), hipMemcpyHostToDevice));
   c->lb_ulps = c->eps_ulps;
   c->lb_proven = c->exact_shadows;
   unsigned long long e = 0, n = 0, g = 0, te = 0, tg = 0, nv = 0, bd = 0, tnv = 0, tbd = 0;
@@ -232,9 +234,31 @@ int lbuf_prepare(rt_hip_ctx* c, hipStream_t s) {
   return RT_OK;
 }
 
+int lbuf_prepare(rt_hip_ctx* c, hipStream_t s) {
+  if (!c->light_buffers || c->accel != RT_ACCEL_OCTREE || !c->d_node || !c->nlight) return RT_OK;
+  if (c->d_lbuf && c->lb_ulps == c->eps_ulps && c->lb_proven == c->exact_shadows) return RT_OK;
+  lbuf_release(c);
+  c->lb_dev.assign(c->nlight, nullptr);
+  c->lb_host.assign(c->nlight, RtLightBuf{});
+  c->lb_failed.assign(c->nlight, 0);
+  c->info.lightbuf_fail_reason[0] = 0;
+  for (uint32_t li = 0; li < c->nlight; li++) {
+    const int rc = lbuf_build_one(c, li, s);
+    if (rc) {
+      for (LBDevice*& d : c->lb_dev) {
+        rt_lightbuf_free(d);
+        d = nullptr;
+      }
+      return rc;
+    }
+  }
+  return lbuf_publish(c);
+}
+
 extern "C" int rt_hip_set_light_buffers(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
   c->light_buffers = enable ? 1 : 0;
+  c->relight.invalidate();  // the kept masks were decided the other way
   if (!c->light_buffers) lbuf_release(c);
   return RT_OK;
 }
@@ -242,6 +266,7 @@ extern "C" int rt_hip_set_light_buffers(rt_hip_ctx* c, int enable) {
 extern "C" int rt_hip_set_lightbuf_entry_cap(rt_hip_ctx* c, unsigned long long cap) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
   c->lb_entry_cap = cap;
+  c->relight.invalidate();
   lbuf_release(c);  // rebuilt (and the cap applied) by the next render
   HIP_TRY(hipSetDevice(c->device));
   return lbuf_prepare(c, c->stream);
@@ -359,6 +384,7 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
   c->info.node_record_bytes = RT_NODE_FLOATS * sizeof(float);
   c->info.device_bytes = bytes_tri + bytes_nrm + bytes_mat + bytes_light + bytes_node;
   c->info.build_seconds = std::chrono::duration<double>(dev_build ? t2 - t0 : t1 - t0).count();
+  if (fs.mat) c->mat_host.assign(fs.mat, fs.mat + fs.nobj * RT_MAT_FLOATS);
   rt_flat_free(&fs);
   if (rc) {
     rt_hip_destroy(c);
@@ -422,6 +448,7 @@ extern "C" int rt_hip_set_cull_slack(rt_hip_ctx* c, float ulps) {
   if (!c || !(ulps >= 0.0f)) return rt_set_error(RT_EINVAL, "bad slack");
   c->eps_ulps = ulps;
   c->cam_eps_ulps = ulps;
+  c->relight.invalidate();
   lists_changed(c);  // the lists change
   return RT_OK;
 }
@@ -442,6 +469,7 @@ extern "C" int rt_hip_set_exact_camera(rt_hip_ctx* c, int enable) {
 extern "C" int rt_hip_set_exact_shadows(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
   c->exact_shadows = enable ? 1 : 0;
+  c->relight.invalidate();
   // built now (setup), reported by rt_hip_accel_info: the light buffers in
   // the matching mode, and the walk's multipliers (policies that walk)
   HIP_TRY(hipSetDevice(c->device));
@@ -498,6 +526,7 @@ extern "C" int rt_hip_set_policy(rt_hip_ctx* c, int policy) {
   if (policy < RT_POLICY_DEFAULT || policy > RT_POLICY_DIR_STAGED)
     return rt_set_error(RT_EINVAL, "unknown traversal policy %d", policy);
   c->policy = policy;
+  c->relight.invalidate();  // (the kept masks are another policy's queries')
   return RT_OK;
 }
 
@@ -519,6 +548,16 @@ extern "C" int rt_hip_set_camera_bound_scale(rt_hip_ctx* c, double scale) {
 // camera ray (the reference scenes make 0.5-1.3; C5 0.48), then for what an
 // overflowing frame needed (rt_hip_stats -> RT_EHITBUF); `last` for every
 // (item, lane).
+// The kept records' mask buffer (KParams::hit_lit): 4 B for every record the
+// hit buffers hold; a new one holds no current bit.
+static int mask_buffer(rt_hip_ctx* c) {
+  const size_t n = c->hit_cap() * RT_HIT_REGIONS;
+  if (c->d_hit_lit.holds(n)) return RT_OK;
+  c->relight.invalidate();
+  HIP_TRY(c->d_hit_lit.alloc(n));
+  return RT_OK;
+}
+
 static int hit_buffers(rt_hip_ctx* c, size_t ntiles) {
   const size_t items = 4 * ntiles;
   HIP_TRY(c->d_last.grow(items * 64, items * 64));
@@ -526,16 +565,19 @@ static int hit_buffers(rt_hip_ctx* c, size_t ntiles) {
   size_t want =(2 * items * 64 + RT_HIT_REGIONS - 1) / RT_HIT_REGIONS + 1024;
   if (c->hit_need > want) want = c->hit_need;
   if (want > (1ull << 29) - 1) want = (1ull << 29) - 1;  // slot field of a record index
-  if (want <= c->hit_cap()) return RT_OK;
-  // all three or none: hit_cap() is what every one of them holds
+  if (want <= c->hit_cap()) return c->keep_visibility ? mask_buffer(c) : RT_OK;
+  // all three or none: hit_cap() is what every one of them holds; the masks
+  // of the records that go (rt_hip_set_keep_visibility, rt_hip_relight) with them
   c->d_hit.reset();
   c->d_hit_prev.reset();
   c->d_hit_term.reset();
+  c->d_hit_lit.reset();
+  c->relight.invalidate();
   const size_t n = want * RT_HIT_REGIONS;
   HIP_TRY(c->d_hit.alloc(2 * n));
   HIP_TRY(c->d_hit_prev.alloc(n));
   HIP_TRY(c->d_hit_term.alloc(n));
-  return RT_OK;
+  return c->keep_visibility ? mask_buffer(c) : RT_OK;
 }
 
 // ---- rt_hip_render, step by step (in the order it runs them) ----
@@ -590,6 +632,14 @@ static int render_done(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hipSt
     c->gb_frame = *f;
     c->gb_valid = 1;
   }
+  // rt_hip_relight may shade this frame's records again; their masks are
+  // current only if this render's shade pass wrote them
+  c->rl_frame = *f;
+  c->rl_valid = 1;
+  if (p.hit_lit)
+    c->relight.masks_written();
+  else
+    c->relight.invalidate();
   if (c->timing) {
     hipEvent_t* ev = c->ev[c->frames % RT_TIMED_FRAMES];
     for (int k = first_ev; k < 5; k++) HIP_TRY(hipEventRecord(ev[k], s));
@@ -619,6 +669,7 @@ static int render_buffers(rt_hip_ctx* c, KParams& p) {
     if (rc) return rc;
   }
   if (c->gbuffer) p.capture = c->d_capture;
+  if (c->keep_visibility) p.hit_lit = c->d_hit_lit;  // the shade pass keeps each record's mask (rt_hip_relight)
   p.hit = c->d_hit;
   p.hit_prev = c->d_hit_prev;
   p.hit_term = c->d_hit_term;
@@ -805,6 +856,7 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   int rc = render_refuse(c, f, rank, nranks, d_tiles);
   if (rc) return rc;
   c->gb_valid = 0;
+  c->rl_valid = 0;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   // lists rt_hip_cand_consume built for exactly this frame and rank: used once
@@ -968,6 +1020,224 @@ extern "C" int rt_hip_render_image(rt_hip_ctx* c, const rt_frame* f, float* h_rg
   return rc;
 }
 
+// ------------------------------------------------------------------ relight
+// Lights and materials edited in place, and the last render's kept hit
+// records shaded again under them (include/rt_hip.h; the bookkeeping is
+// csrc/rt_relight.h, the kernels csrc/rt_recolour.h and shade_kernel).
+
+static std::vector<RelightLight> light_table(const rt_hip_ctx* c) {
+  std::vector<RelightLight> t(c->nlight);
+  for (uint32_t li = 0; li < c->nlight; li++) t[li] = RelightLight(c->light_type[li], &c->light_v[3 * li]);
+  return t;
+}
+
+// Setup calls that free or overwrite what a kernel in flight may read wait
+// for the last render's stream and the context's own first.
+static int relight_quiesce(rt_hip_ctx* c) {
+  if (c->last_stream && c->last_stream != c->stream.s) HIP_TRY(hipStreamSynchronize(c->last_stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+extern "C" int rt_hip_set_lights(rt_hip_ctx* c, const rt_light* lights, size_t n) {
+  if (!c || (n && !lights)) return rt_set_error(RT_EINVAL, "null argument");
+  if (n > 0x7fffffffu / RT_LIGHT_FLOATS) return rt_set_error(RT_EINVAL, "%zu lights", n);
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = relight_quiesce(c);
+  if (rc) return rc;
+  std::vector<float> rows(n * RT_LIGHT_FLOATS, 0.0f), lv(3 * n);
+  std::vector<uint32_t> type(n);
+  for (size_t li = 0; li < n; li++) {  // the rows rt_flatten writes (host/accel.c)
+    const rt_light& l = lights[li];
+    float* L = &rows[RT_LIGHT_FLOATS * li];
+    type[li] = (uint32_t)l.type;
+    std::memcpy(&L[0], &type[li], sizeof(float));
+    L[1] = l.r, L[2] = l.g, L[3] = l.b;
+    L[4] = lv[3 * li] = l.v.x, L[5] = lv[3 * li + 1] = l.v.y, L[6] = lv[3 * li + 2] = l.v.z;
+  }
+  const std::vector<RelightLight> was = light_table(c);
+  const size_t old_n = c->nlight;
+  rc = upload(c->d_light, rows.data(), rows.size() * sizeof(float));
+  if (rc) return rc;
+  c->nlight = (uint32_t)n;
+  c->light_type = type;
+  c->light_v = lv;
+  const std::vector<RelightLight> now = light_table(c);
+  std::vector<uint8_t> rebuild, release;
+  c->relight.set_lights(was, now, rebuild, release);
+  bool edited = was.size() != now.size();
+  for (size_t li = 0; li < now.size() && !edited; li++) edited = !now[li].same(was[li]);
+  if (edited) c->sh_ulps = -1.0f;  // the proven walk's multipliers are per light table (shadow_prepare)
+  // the last render's parameters are views into the context's buffers
+  c->last_p.light = c->d_light;
+  c->last_p.nlight = c->nlight;
+  if (!(c->light_buffers && c->accel == RT_ACCEL_OCTREE && c->d_node)) return RT_OK;  // no light has a buffer
+  const bool current = c->d_lbuf && c->lb_ulps == c->eps_ulps && c->lb_proven == c->exact_shadows &&
+                       c->lb_dev.size() == old_n && c->lb_host.size() == old_n && c->lb_failed.size() == old_n;
+  if (!current || n == 0) {  // every buffer: none is built for this slack and mode, or none is left
+    lbuf_release(c);
+    c->lb_dev.clear();
+    c->lb_host.clear();
+    c->lb_failed.clear();
+    c->last_p.lbuf = nullptr;
+    c->info.lightbuf_entries = c->info.lightbuf_global = c->info.lightbuf_never = c->info.lightbuf_band = 0;
+    c->info.lightbuf_failed = 0;
+    c->info.lightbuf_fail_reason[0] = 0;
+    rc = lbuf_prepare(c, c->stream);
+    if (c->last_p.hit) c->last_p.lbuf = c->d_lbuf;
+    return rc;
+  }
+  for (size_t li = 0; li < old_n; li++)
+    if (release[li]) {
+      rt_lightbuf_free(c->lb_dev[li]);
+      c->lb_dev[li] = nullptr;
+    }
+  c->lb_dev.resize(n, nullptr);
+  c->lb_host.resize(n, RtLightBuf{});
+  c->lb_failed.resize(n, 0);
+  for (uint32_t li = 0; li < n; li++) {
+    if (!now[li].casts()) {  // (its buffer, if it had one, was released)
+      c->lb_host[li] = RtLightBuf{};
+      c->lb_failed[li] = 0;
+    }
+    if (!rebuild[li]) continue;
+    rc = lbuf_build_one(c, li, c->stream);
+    if (rc) {  // a failed launch: no buffer is trusted, the next render builds them all
+      lbuf_release(c);
+      c->last_p.lbuf = nullptr;
+      return rc;
+    }
+  }
+  rc = lbuf_publish(c);
+  c->last_p.lbuf = c->last_p.lbuf ? c->d_lbuf.get() : nullptr;
+  return rc;
+}
+
+extern "C" int rt_hip_set_materials(rt_hip_ctx* c, const rt_object* objects, size_t n) {
+  if (!c || (n && !objects)) return rt_set_error(RT_EINVAL, "null argument");
+  if (n * RT_MAT_FLOATS != c->mat_host.size())
+    return rt_set_error(RT_EINVAL, "%zu objects, the context has %zu", n, c->mat_host.size() / RT_MAT_FLOATS);
+  std::vector<float> rows(c->mat_host.size(), 0.0f);
+  for (size_t o = 0; o < n; o++) {  // the rows rt_flatten writes (host/accel.c)
+    const rt_object& ob = objects[o];
+    float* m = &rows[RT_MAT_FLOATS * o];
+    m[0] = ob.ka.x, m[1] = ob.ka.y, m[2] = ob.ka.z;
+    m[3] = ob.kd.x, m[4] = ob.kd.y, m[5] = ob.kd.z;
+    m[6] = ob.ks.x, m[7] = ob.ks.y, m[8] = ob.ks.z;
+    m[9] = ob.ns;
+    m[10] = ob.nr;
+    // what the trace reads of the row (trace_path: obj.nr * coef) decides the
+    // paths: it must be what the kept records were traced with
+    if (std::memcmp(&m[10], &c->mat_host[RT_MAT_FLOATS * o + 10], 2 * sizeof(float)) != 0)
+      return rt_set_error(RT_EINVAL, "object %zu: nr %g differs from the context's %g (reflectivity changes the paths: "
+                          "create a new context)", o, (double)ob.nr, (double)c->mat_host[RT_MAT_FLOATS * o + 10]);
+  }
+  if (!n) return RT_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = relight_quiesce(c);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(c->d_mat, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+  c->mat_host = rows;
+  return RT_OK;
+}
+
+extern "C" int rt_hip_set_keep_visibility(rt_hip_ctx* c, int enable) {
+  if (!c) return rt_set_error(RT_EINVAL, "null context");
+  c->keep_visibility = enable ? 1 : 0;  // (the mask buffer comes with the next render's hit buffers)
+  return RT_OK;
+}
+
+extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, float* d_tiles,
+                              void* stream) {
+  if (!c || !f || !d_tiles) return rt_set_error(RT_EINVAL, "null argument");
+  // the refusals: nothing of the context has changed when one of them returns
+  if (!c->rl_valid)
+    return rt_set_error(RT_EINVAL, "no kept hit records: rt_hip_render first (rt_hip_render_compat keeps none)");
+  const KParams& lp = c->last_p;
+  if (lp.rank != rank || lp.nranks != nranks || std::memcmp(&c->rl_frame, f, sizeof *f) != 0)
+    return rt_set_error(RT_EINVAL, "the kept records are another frame's (last render: %dx%d, rank %d of %d)", lp.W,
+                        lp.H, lp.rank, lp.nranks);
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (s != c->last_stream) return rt_set_error(RT_EINVAL, "a relight runs on the stream of its render");
+  if (c->policy != RT_POLICY_DEFAULT)
+    return rt_set_error(RT_EINVAL, "a relight needs the default traversal policy (have %d)", c->policy);
+  if (c->count_work) return rt_set_error(RT_EINVAL, "a relight cannot run as the work-counting pass");
+  if (lp.ntiles_local == 0) return RT_OK;  // a rank past the last block: nothing rendered, nothing written
+  HIP_TRY(hipSetDevice(c->device));
+  // the render's parameters with the scene as it is now and nothing of the
+  // render's shadow set-up (rebuilt below for the current lights and mode)
+  KParams p = lp;
+  {
+    const KParams sp = scene_params(c);
+    p.light = sp.light;
+    p.nlight = sp.nlight;
+    p.mat = sp.mat;
+    p.eps_rel = sp.eps_rel;
+    p.eps_rel_cam = sp.eps_rel_cam;
+  }
+  p.out = d_tiles;
+  p.lbuf = nullptr;
+  p.node_mu = nullptr;
+  p.sh_global = nullptr;
+  p.n_sh_global = 0;
+  p.sh_omax = 0.0f;
+  p.oob = nullptr;
+  p.oob_count = nullptr;
+  p.oob_cap = 0;
+  p.shade_stride = p.shade_first = 0;
+  p.relight_dirty = 0;
+  // the fold's frame check counts renders only (rt_hip_frame_check)
+  p.frame_check = nullptr;
+  p.list_flag = nullptr;
+  int rc = mask_buffer(c);  // (a new one: every bit is stale, the full shade writes them)
+  if (rc) return rc;
+  p.hit_lit = c->d_hit_lit;
+  RenderKernels k;
+  if ((rc = render_shadows(c, p, s)) || (rc = render_kernels(c, p, s, &k))) return rc;
+  const RelightWork w = c->relight.work(light_table(c));
+  if (w.path == RT_RELIGHT_RECOLOUR) p.oob = nullptr;  // no query, so none deferred: no fixup
+  // every device pointer the kernels will follow must exist (a null one
+  // would fault the card, not fail the call)
+  if (!p.tri_prim && (p.lbuf || p.n_sh_global)) return rt_set_error(RT_EHIP, "relight: prim-order records missing");
+  if (!p.hit || !p.hit_prev || !p.hit_term || !p.hit_lit || !p.hit_count || !p.shade_counter || !p.stats ||
+      !p.last || !p.out || (p.nlight && !p.light) || (p.nrec && (!p.tri || !p.nrm)) || !p.mat ||
+      p.hit_cap != c->hit_cap() || !c->d_hit_lit.holds((size_t)p.hit_cap * RT_HIT_REGIONS))
+    return rt_set_error(RT_EHIP, "relight: device buffers missing");
+  HIP_TRY(rt_launch_relight_zero(&p, s));
+  if (w.path == RT_RELIGHT_RECOLOUR) {
+    HIP_TRY(rt_launch_recolour(&p, c->cus, s));
+  } else if (w.path == RT_RELIGHT_PARTIAL) {
+    p.relight_dirty = w.dirty;
+    HIP_TRY(rt_launch_reshade(&p, k.dacc, k.spol, k.gs, s));
+  } else {
+    HIP_TRY(rt_launch_shade(&p, k.dacc, 0, k.spol, k.gs, s));
+  }
+  HIP_TRY(rt_launch_shade_fixup(&p, c->nprim, s));
+  HIP_TRY(rt_launch_fold(&p, s));
+  c->relight.masks_written();
+  c->last_p = p;  // rt_hip_stats (the deferred count), rt_hip_verify_shadows, rt_hip_gbuffer (its fields are the render's)
+  return RT_OK;
+}
+
+extern "C" int rt_hip_relight_image(rt_hip_ctx* c, const rt_frame* f, float* h_rgb, rt_stats* st) {
+  if (!c || !f || !h_rgb) return rt_set_error(RT_EINVAL, "null argument");
+  if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t nt = rt_hip_tile_buffer_floats(f->width, f->height, 1);
+  const size_t npx = (size_t)f->width * f->height;
+  DevBuf<float> d_tiles, d_rgb;
+  HIP_TRY(d_tiles.alloc(nt));
+  if (d_rgb.alloc(npx * 3) != hipSuccess) return rt_set_error(RT_EHIP, "hipMalloc image");
+  rt_stats tmp;
+  int rc = rt_hip_relight(c, f, 0, 1, d_tiles, nullptr);
+  if (rc) return rc;
+  rc = rt_hip_assemble(c, f, d_tiles, 1, d_rgb, nullptr);
+  if (!rc && hipMemcpyAsync(h_rgb, d_rgb, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+    rc = rt_set_error(RT_EHIP, "D2H image");
+  const int src = rt_hip_stats(c, st ? st : &tmp);  // (synchronises: the buffers above may go)
+  return rc ? rc : src;
+}
+
 // ----------------------------------------------------------------- G-buffer
 static_assert(RT_GB_WORDS == RT_GB_WORDS_D && sizeof(rt_gsample) == 4 * RT_GB_WORDS,
               "rt_gsample is the record gbuffer_kernel writes");
@@ -1110,6 +1380,8 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
     if (rc) return rc;
   }
   c->cost_hist.valid = 0;  // the counters are the compat render's
+  c->rl_valid = 0;         // (and no hit records are kept: nothing to relight)
+  c->relight.invalidate();
   if (hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s) != hipSuccess ||
       rt_launch_compat(&p, accel, c->grid, s) != hipSuccess ||
       rt_launch_downscale(d_hi, d_lo, cam->width, cam->height, s) != hipSuccess ||

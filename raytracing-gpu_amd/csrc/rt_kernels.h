@@ -193,8 +193,12 @@ struct KParams {
   // G-buffer capture (RT_POLICY_GBUFFER; NULL otherwise), per (item, lane) like
   // `last`: the camera query's winner prim (~0: none) | bits of its new_dist |
   // the path's first hit record (RT_NO_REC: none) | the path's closest-hit
-  // queries.  The last member: every other kernel's argument offsets stay put
+  // queries.  Appended: every other kernel's argument offsets stay put
   uint4* capture;
+  // relight (rt_hip_relight, shade_kernel's relight instantiation only): the
+  // lights 0..31 whose shadow queries run; the others' outcomes are the bits
+  // of the record's stored mask hit_lit (csrc/rt_relight.h).  Appended too
+  uint32_t relight_dirty;
 };
 #define RT_FRAME_HITBUF 1u     // hit records past a region's capacity
 #define RT_FRAME_DEPTH 2u      // bounce limit or traversal stack overflow
@@ -213,6 +217,16 @@ extern "C" hipError_t rt_launch_shade(const KParams* p, int accel, int count_wor
 // force over the nprim prim-order records, then their records re-shaded
 extern "C" hipError_t rt_launch_shade_fixup(const KParams* p, uint32_t nprim, hipStream_t stream);
 extern "C" hipError_t rt_launch_fold(const KParams* p, hipStream_t stream);
+// relight (csrc/rt_recolour.h): the kept records of the last render shaded
+// again.  rt_launch_relight_zero zeroes what a shade pass adds to -- the shade
+// chunk counters, the shadow-side stat slots, the off-box queue's count --
+// and leaves the trace's counters; rt_launch_recolour sums every record's
+// lights from its stored mask p->hit_lit (no shadow query); rt_launch_reshade
+// is shade_kernel querying only the lights of p->relight_dirty (default
+// policy, RT_POLICY_LBUF or FLAT; no counting variant)
+extern "C" hipError_t rt_launch_relight_zero(const KParams* p, hipStream_t stream);
+extern "C" hipError_t rt_launch_recolour(const KParams* p, int cus, hipStream_t stream);
+extern "C" hipError_t rt_launch_reshade(const KParams* p, int accel, int policy, int grid, hipStream_t stream);
 // shadow-query probe: light li's shadow ray from each of n origins through
 // the light buffer p->lbuf[li] (brute = 0) or brute force over nprim
 // prim-order records p->tri_prim (brute = 1); out[i] = shadowed

@@ -319,7 +319,11 @@ static constexpr int kLaneStackArea = kLdsStack * 64 * 8 / 16;
 // of 32 lights: first the shadow queries (only the hit point is live across
 // the walks), then the Phong terms of the unshadowed lights, summed in the
 // file order of the lights as the reference does.
-template <int ACCEL, bool COUNT, int POL>
+// RELIGHT (rt_hip_relight with some lights clean, csrc/rt_relight.h): only the
+// lights of p.relight_dirty among 0..31 are queried, the others' bits come
+// from the record's stored mask p.hit_lit; lights from index 32 up have no
+// stored bit and are always queried.
+template <int ACCEL, bool COUNT, int POL, bool RELIGHT = false>
 __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t a, Stack& s,
                                             WaveCtx& w, WorkCount& wc, uint32_t& lit0) {
   col acc = init_color(0.0f, 0.0f, 0.0f);
@@ -327,6 +331,8 @@ __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t
   for (uint32_t l0 = 0; l0 < p.nlight; l0 += 32) {
     const uint32_t l1 = p.nlight - l0 < 32u ? p.nlight : l0 + 32u;
     uint32_t lit = 0;  // bit k: light l0 + k does not shadow the point
+    if constexpr (RELIGHT)
+      if (valid && l0 == 0) lit = p.hit_lit[a] & ~p.relight_dirty;  // the clean lights' decisions
     {
       f3 P{0.0f, 0.0f, 0.0f};
       if (valid) {
@@ -337,6 +343,8 @@ __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t
         const float* L = p.light + RT_LIGHT_FLOATS_D * li;
         const uint32_t type = __float_as_uint(L[0]);
         if (type != 1 && type != 2) continue;
+        if constexpr (RELIGHT)
+          if (l0 == 0 && !((p.relight_dirty >> li) & 1u)) continue;  // clean: no query (wave-uniform)
         const f3 lv = f3{L[4], L[5], L[6]};
         const uint64_t c0 = COUNT ? __builtin_readcyclecounter() : 0ull;
         bool df = false;
@@ -368,15 +376,7 @@ __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t
     const float4 r0 = p.hit[2 * a], r1 = p.hit[2 * a + 1];
     const f3 P{r0.x, r0.y, r0.z}, N{r0.w, r1.x, r1.y};
     const float* m = p.mat + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
-    for (uint32_t li = l0; li < l1; li++) {
-      const float* L = p.light + RT_LIGHT_FLOATS_D * li;
-      const uint32_t type = __float_as_uint(L[0]);
-      const col lc = init_color(L[1], L[2], L[3]);
-      if (type == 0)  // AMBIENT
-        acc = color_add(acc, color_mul2(lc, init_color(m[0], m[1], m[2])));
-      else if ((type == 1 || type == 2) && ((lit >> (li - l0)) & 1u))
-        acc = color_add(acc, light_lit(type, lc, f3{L[4], L[5], L[6]}, m, P, N));
-    }
+    acc = lights_sum(p.light, acc, l0, l1, lit, m, P, N);
   }
   return acc;
 }
@@ -385,7 +385,7 @@ __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t
 // (workgroup b drains region b mod 8, then steals), every lane one record:
 // cpu/light.c:33-100 with the shadow queries of cpu/light.c:24-31, then the
 // term color_mul(local, coef) of cpu/raytracer.c:30.
-template <int ACCEL, bool COUNT, int POL>
+template <int ACCEL, bool COUNT, int POL, bool RELIGHT = false>
 __global__ __launch_bounds__(64, ACCEL == RT_ACCEL_FLAT_D ? RT_FLAT_SHADE_MIN_WAVES
                                 : ((POL == RT_POLICY_STAGED || POL == RT_POLICY_DIR_STAGED) ? RT_STAGED_SHADE_MIN_WAVES
                                                                                               : RT_SHADE_MIN_WAVES)) void shade_kernel(KParams p) {
@@ -434,7 +434,7 @@ __global__ __launch_bounds__(64, ACCEL == RT_ACCEL_FLAT_D ? RT_FLAT_SHADE_MIN_WA
     const bool valid = k < ns;
     const size_t a = (size_t)x * p.hit_cap + (size_t)k * stride + first;
     uint32_t lit = 0;
-    const col local = shade_record<ACCEL, COUNT, POL>(p, valid, a, stk, w, wc, lit);
+    const col local = shade_record<ACCEL, COUNT, POL, RELIGHT>(p, valid, a, stk, w, wc, lit);
     if (valid) {
       const col tm = color_mul(local, p.hit[2 * a + 1].z);  // coef
       p.hit_term[a] = make_float4(tm.r, tm.g, tm.b, 0.0f);
@@ -559,16 +559,8 @@ __global__ __launch_bounds__(64) void oob_reshade_kernel(KParams p) {
     const float4 r0 = p.hit[2 * a], r1 = p.hit[2 * a + 1];
     const f3 P{r0.x, r0.y, r0.z}, N{r0.w, r1.x, r1.y};
     const float* m = p.mat + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
-    col acc = init_color(0.0f, 0.0f, 0.0f);
-    for (uint32_t li = 0; li < p.nlight && li < 32; li++) {
-      const float* L = p.light + RT_LIGHT_FLOATS_D * li;
-      const uint32_t type = __float_as_uint(L[0]);
-      const col lc = init_color(L[1], L[2], L[3]);
-      if (type == 0)  // AMBIENT
-        acc = color_add(acc, color_mul2(lc, init_color(m[0], m[1], m[2])));
-      else if ((type == 1 || type == 2) && ((lit0 >> li) & 1u))
-        acc = color_add(acc, light_lit(type, lc, f3{L[4], L[5], L[6]}, m, P, N));
-    }
+    const col acc =
+        lights_sum(p.light, init_color(0.0f, 0.0f, 0.0f), 0, p.nlight < 32u ? p.nlight : 32u, lit0, m, P, N);
     const col tm = color_mul(acc, r1.z);  // coef
     p.hit_term[a] = make_float4(tm.r, tm.g, tm.b, 0.0f);
     if (p.hit_lit) p.hit_lit[a] = lit0;
@@ -721,6 +713,8 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
 }
 
 }  // namespace rt
+
+#include "rt_recolour.h"  // relight_zero_kernel, recolour_kernel: after every render kernel
 
 // ---------------------------------------------------------------- launchers
 // One instantiation per (kernel, accel, work counting, policy); the default
@@ -875,4 +869,34 @@ extern "C" hipError_t rt_launch_downscale(const uint32_t* hi, uint32_t* lo, int 
   const int n = W * H;
   hipLaunchKernelGGL(rt::downscale_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, hi, lo, W, H);
   return hipGetLastError();
+}
+
+// The relight's launches (rt_kernels.h).  shade_kernel's relight
+// instantiations are separate kernels, like the counting and test ones: the
+// default shade kernels have no switch for them.  Last in the file, and
+// relight_zero_kernel / recolour_kernel templates, so that all of them are
+// emitted after every other kernel: the render kernels keep their places in
+// the code object.
+extern "C" hipError_t rt_launch_relight_zero(const KParams* p, hipStream_t stream) {
+  hipLaunchKernelGGL((rt::relight_zero_kernel<0>), dim3(1), dim3(256), 0, stream, *p);
+  return hipGetLastError();
+}
+
+// A streaming kernel: one 256-lane workgroup per 256 records the buffers can
+// hold, at most 8 workgroups per CU, the rest by grid stride.
+extern "C" hipError_t rt_launch_recolour(const KParams* p, int cus, hipStream_t stream) {
+  const unsigned long long blocks = ((unsigned long long)p->hit_cap * RT_HIT_REGIONS + 255) / 256;
+  const unsigned long long most = 8ull * (cus > 0 ? cus : 1);
+  hipLaunchKernelGGL((rt::recolour_kernel<0>), dim3((unsigned)(blocks < most ? (blocks ? blocks : 1) : most)), dim3(256), 0,
+                     stream, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_reshade(const KParams* p, int accel, int policy, int grid, hipStream_t stream) {
+  using namespace rt;
+  const void* k = accel == RT_ACCEL_FLAT_D ? (const void*)shade_kernel<RT_ACCEL_FLAT_D, false, 0, true>
+                  : policy == RT_POLICY_LBUF
+                      ? (const void*)shade_kernel<RT_ACCEL_OCTREE_D, false, RT_POLICY_LBUF, true>
+                      : (const void*)shade_kernel<RT_ACCEL_OCTREE_D, false, RT_POLICY_DEFAULT, true>;
+  return launch_kernel(k, grid, p, stream);
 }

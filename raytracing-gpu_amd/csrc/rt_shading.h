@@ -59,6 +59,26 @@ __device__ __forceinline__ col light_lit(uint32_t type, col lc, f3 lv, const flo
   return specular(tmp, inc_o, to_l, P, N, m);
 }
 
+// The lights l0 .. l1 - 1 of a record summed onto acc in the file order of the
+// lights (light = the table, RT_LIGHT_FLOATS_D floats each, in global memory
+// or staged in LDS), as cpu/light.c:33-100 does: an ambient light's term, and a
+// directional or point light's when bit li - l0 of `lit` says no shadow ray hit.
+// The one per-record sum of shade_record's second phase, oob_reshade_kernel
+// and recolour_kernel (rt_recolour.h), so the three cannot drift.
+__device__ __forceinline__ col lights_sum(const float* light, col acc, uint32_t l0, uint32_t l1, uint32_t lit,
+                                          const float* m, f3 P, f3 N) {
+  for (uint32_t li = l0; li < l1; li++) {
+    const float* L = light + RT_LIGHT_FLOATS_D * li;
+    const uint32_t type = __float_as_uint(L[0]);
+    const col lc = init_color(L[1], L[2], L[3]);
+    if (type == 0)  // AMBIENT
+      acc = color_add(acc, color_mul2(lc, init_color(m[0], m[1], m[2])));
+    else if ((type == 1 || type == 2) && ((lit >> (li - l0)) & 1u))
+      acc = color_add(acc, light_lit(type, lc, f3{L[4], L[5], L[6]}, m, P, N));
+  }
+  return acc;
+}
+
 // cpu/light.c:33-100 for the lanes with hit.  The light loop is wave-uniform
 // so shadow queries run converged.
 template <int ACCEL, bool COUNT, int POL>

@@ -200,6 +200,11 @@ _PROTOS = [
                                       C.c_uint, C.c_void_p]),
     ("rt_hip_render_image", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p,
                                       C.POINTER(Stats)]),
+    ("rt_hip_set_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("rt_hip_set_materials", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("rt_hip_set_keep_visibility", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_hip_relight", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("rt_hip_relight_image", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.POINTER(Stats)]),
     ("rt_hip_set_gbuffer", C.c_int, [C.c_void_p, C.c_int]),
     ("rt_hip_gbuffer_tile_words", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     ("rt_hip_gbuffer", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -314,6 +319,15 @@ class Scene:
 
     def materials_array(self):
         return scene_materials(self.ptr)
+
+    def lights(self):
+        """The scene's own light array as a ctypes (Light * light_count) view:
+        edits change the scene (what an oracle given the same rt_scene renders,
+        and what Context.set_lights(scene.lights()) uploads)."""
+        n = int(self.s.light_count)
+        if n == 0:
+            return (Light * 0)()
+        return (Light * n).from_address(C.addressof(self.s.lights.contents))
 
     def lightbuf_survey(self, light, exact=False, stride=1):
         """Host-only count of light `light`'s buffer (rt_lightbuf_survey)."""
@@ -709,6 +723,49 @@ class Context:
         self._check_render(lib().rt_hip_render_image(self.h, C.byref(frame),
                                                      img.ctypes.data_as(C.c_void_p), C.byref(st)),
                            "rt_hip_render_image")
+        return img, st.as_dict()
+
+    def set_lights(self, lights):
+        """Replace the light table (rt_hip_set_lights): a ctypes Light array
+        (e.g. Scene.lights()) or a sequence of (type, r, g, b, x, y, z).  Only
+        the buffers of lights whose (type, position) changed are rebuilt."""
+        if not isinstance(lights, C.Array):
+            rows = list(lights)
+            arr = (Light * len(rows))()
+            for l, (t, r, g, b, x, y, z) in zip(arr, rows):
+                l.type, l.r, l.g, l.b = int(t), r, g, b
+                l.v.x, l.v.y, l.v.z = x, y, z
+            lights = arr
+        _check(lib().rt_hip_set_lights(self.h, C.cast(lights, C.c_void_p), len(lights)), "rt_hip_set_lights")
+
+    def set_materials(self, scene_or_objects):
+        """ka, kd, ks, ns of every object (rt_hip_set_materials) from a Scene
+        or a ctypes Object array; nr must be what the context was created with."""
+        if isinstance(scene_or_objects, Scene):
+            s = scene_or_objects.s
+            ptr, n = C.cast(s.objects, C.c_void_p), int(s.object_count)
+        else:
+            ptr, n = C.cast(scene_or_objects, C.c_void_p), len(scene_or_objects)
+        _check(lib().rt_hip_set_materials(self.h, ptr, n), "rt_hip_set_materials")
+
+    def set_keep_visibility(self, on=True):
+        """Renders keep each hit record's unshadowed-light mask, so the first
+        relight can already skip shadow queries (rt_hip_set_keep_visibility)."""
+        _check(lib().rt_hip_set_keep_visibility(self.h, 1 if on else 0), "rt_hip_set_keep_visibility")
+
+    def relight(self, frame, rank, nranks, d_tiles, stream=None):
+        """The last render's kept hit records shaded again under the current
+        lights and materials, folded into d_tiles (rt_hip_relight)."""
+        _check(lib().rt_hip_relight(self.h, C.byref(frame), rank, nranks, C.c_void_p(d_tiles),
+                                    C.c_void_p(stream) if stream else None), "rt_hip_relight")
+
+    def relight_image(self, frame):
+        """relight() of the whole frame after render_image(frame) -> (H, W, 3)
+        float32 in PPM order, stats (rt_hip_relight_image)."""
+        img = np.empty((frame.height, frame.width, 3), np.float32)
+        st = Stats()
+        self._check_render(lib().rt_hip_relight_image(self.h, C.byref(frame), img.ctypes.data_as(C.c_void_p),
+                                                      C.byref(st)), "rt_hip_relight_image")
         return img, st.as_dict()
 
     def set_gbuffer(self, on=True):
