@@ -46,9 +46,9 @@ int rt_hip_accel_validate(const rt_hip_ctx *ctx);
 int rt_tile_map_check(int width, int height, int nranks, int maxw, unsigned long long out[2]);
 /* The same conditions checked on the device at the end of every render (no
  * host wait), sticky until read: *flags = their OR since the last call (0 =
- * every frame complete and exact; bits RT_FRAME_* of csrc/rt_kernels.h: 1
- * hit-record overflow, 2 depth, 4 zero normal, 8 undecided exact shadow
- * queries, 16 an asynchronous list build's overflow), *frames = renders
+ * every frame complete and exact; bits RT_FRAME_* of csrc/rt_counters.h: 1
+ * hit-record overflow, 2 depth, 4 zero normal, 8 unproven or undecided exact
+ * shadow / reflection queries, 16 an asynchronous list build's overflow), *frames = renders
  * checked, queries[0] / [1] = their closest-hit / shadow queries; all reset.
  * For callers that render many frames between rt_hip_stats calls. */
 int rt_hip_frame_check(rt_hip_ctx *ctx, unsigned *flags, unsigned *frames, unsigned long long queries[2]);

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_counters.h"
+
 namespace rtc {
 struct Footprint;
 }
@@ -69,10 +71,7 @@ struct CandParams {
   uint32_t* keys;         // entries: local tile index (pass 2)
   uint32_t* vals;         // entries: prim
   uint32_t* global;       // nprim: prims whose footprint is unbounded
-  uint32_t* ctr;          // [1] global prims, [2] big footprints, [3] list length,
-                          // [4] big emission items (item_kernel),
-                          // [5] 1 = more than item_cap items (big_kernel emits instead),
-                          // [6] the entry total, [7] 1 = an entry past key_cap
+  uint32_t* ctr;          // RT_CC_BUILD_WORDS: the build's counters (rt_counters.h RtCandCtr)
   uint32_t* big;          // nprim: list entries with big footprints (rt_cand.hip kSmallRows)
   float* skip;            // nprim: depth-skip bound of each listed prim
   uint32_t* big_lane;     // big_cap x 64: per big footprint, each lane's row-count subtotal
@@ -90,7 +89,7 @@ struct CandParams {
   // entries the key / value buffers hold (0: sized to the frame's exact total
   // by a host read-back, no check).  Asynchronous builds size them from the
   // previous frame's total: an entry past key_cap is not written and sets
-  // ctr[7] (rt_hip_stats then reports the frame and grows the buffers)
+  // ctr[RT_CC_OVERFLOW] (rt_hip_stats then reports the frame and grows the buffers)
   uint32_t key_cap;
 };
 
@@ -126,7 +125,7 @@ extern "C" hipError_t rt_cand_emit(const CandParams* p, hipStream_t s);
 extern "C" hipError_t rt_cand_big(const CandParams* p, uint32_t nbig, hipStream_t s);
 // big emission work items: wave_items (big_count_kernel) -> scan -> wave_base
 // -> rt_cand_items writes them; pass 2b, entry-parallel: one wave per
-// (big footprint, chunk of its entries) item (used when ctr[5] == 0)
+// (big footprint, chunk of its entries) item (used when ctr[RT_CC_ITEMS_OVER] == 0)
 extern "C" uint32_t rt_cand_big_waves(void);
 extern "C" hipError_t rt_cand_items(const CandParams* p, hipStream_t s);
 extern "C" hipError_t rt_cand_big_items(const CandParams* p, uint32_t nitems, int check, hipStream_t s);
@@ -139,7 +138,7 @@ extern "C" uint32_t rt_cand_scan_dev_tiles(uint32_t nmax);
 extern "C" hipError_t rt_cand_scan_dev(const uint32_t* in, uint32_t* out, uint32_t nmax, const uint32_t* n_dev,
                                        uint32_t* total, uint32_t* bsum, hipStream_t s);
 // the fast path's flags (p->visits over the slice) scanned straight into the
-// compact list (p->list) and its length (p->ctr[3]): scan_dev + scatter fused
+// compact list (p->list) and its length (p->ctr[RT_CC_LIST]): scan_dev + scatter fused
 extern "C" hipError_t rt_cand_scan_scatter(const CandParams* p, uint32_t* bsum, hipStream_t s);
 extern "C" hipError_t rt_cand_sort(uint32_t* keys_in, uint32_t* keys_out, uint32_t* vals_in,
                                    uint32_t* vals_out, uint32_t n, int begin_bit, int end_bit, void* temp,
@@ -150,7 +149,7 @@ extern "C" hipError_t rt_cand_fill_tail(uint32_t* keys, const uint32_t* total_de
                                         hipStream_t s);
 extern "C" hipError_t rt_cand_entry_skip(const uint32_t* cand, const float* skip, float* out,
                                          uint32_t n, const uint32_t* n_dev, hipStream_t s);
-// snap (optional): the build's counters, ctr[0 .. 7] copied to [16 .. 23]
+// snap (optional): the counter block, its build words copied to its snapshot region
 extern "C" hipError_t rt_cand_bounds(const uint32_t* keys, uint32_t n, uint32_t* start,
                                      uint32_t ntiles, uint32_t* snap, hipStream_t s);
 // Triangle-parallel multi-GPU lists (rt_hip_cand_produce / rt_hip_cand_consume):
@@ -167,8 +166,8 @@ extern "C" hipError_t rt_cand_route_globals(const uint32_t* global, uint32_t ngl
                                             uint32_t tbits, uint32_t* keys, uint32_t* vals, hipStream_t s);
 // Stable partition of n routed keys by rank (rank nranks: dropped), packed
 // 3 words per entry in out (the dropped ones not written), start[d] = first
-// entry of rank d (start[nranks] = the routed entries; start[nranks + 1 ..
-// nranks + 8] = ctr[0 .. 7], for one read-back): part_count ->
+// entry of rank d (start[nranks] = the routed entries; from
+// start[rt_rstart_ctr(nranks)] on the build's counters, for one read-back): part_count ->
 // hist[(nranks + 1) x rt_cand_part_waves(n)] -> exclusive scan (off) ->
 // part_scatter.  nranks <= 256.
 extern "C" uint32_t rt_cand_part_waves(uint32_t n);
@@ -182,14 +181,14 @@ extern "C" hipError_t rt_cand_part_scatter(const uint32_t* keys, const uint32_t*
                                            uint32_t n, uint32_t tbits, int nranks, const uint32_t* off,
                                            uint32_t* start, uint32_t* out, const uint32_t* ctr, hipStream_t s);
 // Stable compaction of the entries whose key is not drop_key into
-// keys_out / vals_out (at most cap; beyond it *ctr7 = 1; a shorter result's
+// keys_out / vals_out (at most cap; beyond it *over_flag = 1; a shorter result's
 // tail up to cap written as drop_key; n_dev (optional): only the first
 // *n_dev of the n entries are the build's): per-wave counts
 // (cnt, rt_cand_part_waves(n) + 1 words) -> exclusive scan (off, off[nw] =
 // the kept total) -> scatter.  tmp == NULL: *tmp_bytes = the scan's need.
 extern "C" hipError_t rt_cand_compact(const uint32_t* keys, const uint32_t* vals, uint32_t n, const uint32_t* n_dev,
                                       uint32_t drop_key, uint32_t cap, uint32_t* cnt, uint32_t* off, void* tmp,
-                                      size_t* tmp_bytes, uint32_t* keys_out, uint32_t* vals_out, uint32_t* ctr7,
+                                      size_t* tmp_bytes, uint32_t* keys_out, uint32_t* vals_out, uint32_t* over_flag,
                                       hipStream_t s);
 extern "C" hipError_t rt_cand_unpack(const uint32_t* in, uint32_t n, uint32_t ntiles, uint32_t tpr, uint32_t* keys,
                                      uint32_t* idx, hipStream_t s);

@@ -959,7 +959,7 @@ __device__ __forceinline__ uint32_t slice_prim(const CandParams& p, uint32_t i) 
 __global__ __launch_bounds__(RT_LIST_BLOCK, RT_QUICK_WAVES) void quick_kernel(CandParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // index in the slice
   const uint32_t len = p.prim1 - p.prim0;
-  if (i < 8u) p.ctr[i] = 0u;          // the frame's counters (count / big passes, later launches)
+  if (i < RT_CC_BUILD_WORDS) p.ctr[i] = 0u;          // the frame's counters (count / big passes, later launches)
   if (i == 0u) p.visits[len] = 0u;    // the scan's last input
   if (i >= len) return;
   p.visits[i] = quick_class(p, (const float*)(p.tri + 3 * (size_t)slice_prim(p, i))) == Q_LIST ? 1u : 0u;
@@ -1027,7 +1027,7 @@ __device__ __forceinline__ void count_one(const CandParams& p, uint32_t j) {
   const float* lb = p.prim_leaf ? (const float*)(p.node + 2 * (size_t)p.prim_leaf[prim]) : nullptr;
   const int c = classify(p, rec, lb, fp);
   if (c == GLOBAL) {
-    p.global[atomicAdd(p.ctr + 1, 1u)] = prim;
+    p.global[atomicAdd(p.ctr + RT_CC_GLOBAL, 1u)] = prim;
     p.skip[prim] = -1e30f;
   } else if (c == FOOTPRINT) {
     p.skip[prim] = fp.skip;
@@ -1043,7 +1043,7 @@ __device__ __forceinline__ void count_one(const CandParams& p, uint32_t j) {
     } else {
       p.fp[j] = fp;
       if (p.sfp) p.sfp[2 * (size_t)j] = make_uint4(0xffffffffu, 0u, 0u, 0u);  // big: not emit_kernel's
-      p.big[atomicAdd(p.ctr + 2, 1u)] = j;
+      p.big[atomicAdd(p.ctr + RT_CC_BIG, 1u)] = j;
       visits = 0;  // big_count_kernel
     }
   }
@@ -1055,7 +1055,7 @@ __device__ __forceinline__ void count_one(const CandParams& p, uint32_t j) {
 #endif
 __global__ __launch_bounds__(RT_LIST_BLOCK, RT_COUNT_WAVES) void count_kernel(CandParams p) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < p.ctr[3]) count_one(p, j);
+  if (j < p.ctr[RT_CC_LIST]) count_one(p, j);
 }
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
@@ -1076,7 +1076,7 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t x, int lane) {
 // Pass 1b: one wave per big footprint, its tile rows over the lanes.
 __global__ __launch_bounds__(64) void big_count_kernel(CandParams p) {
   const int lane = threadIdx.x;
-  const uint32_t nbig = p.ctr[2];
+  const uint32_t nbig = p.ctr[RT_CC_BIG];
   uint32_t witems = 0;
   for (uint32_t b = blockIdx.x; b < nbig; b += gridDim.x) {
     const uint32_t j = p.big[b];
@@ -1097,19 +1097,19 @@ __global__ __launch_bounds__(64) void big_count_kernel(CandParams p) {
 }
 
 // After the scan of wave_items: each big_count wave's footprints, in the same
-// order, write their items from the wave's offset; past item_cap, ctr[5] = 1
+// order, write their items from the wave's offset; past item_cap, ctr[RT_CC_ITEMS_OVER] = 1
 // and the host emits with big_kernel instead.
 __global__ __launch_bounds__(64) void item_kernel(CandParams p) {
   const int lane = threadIdx.x;
-  const uint32_t nbig = p.ctr[2];
+  const uint32_t nbig = p.ctr[RT_CC_BIG];
   uint32_t at = p.wave_base[blockIdx.x];
-  if (blockIdx.x == 0 && lane == 0) p.ctr[4] = p.wave_base[kBigWaves];  // all items (read back with ctr[])
+  if (blockIdx.x == 0 && lane == 0) p.ctr[RT_CC_ITEMS] = p.wave_base[kBigWaves];  // all items (read back with ctr[])
   for (uint32_t b = blockIdx.x; b < nbig; b += gridDim.x) {
     const uint32_t ni = (p.visits[p.big[b]] + (1u << p.chunk_shift) - 1) >> p.chunk_shift;
     if (at + ni <= p.item_cap) {
       for (uint32_t c = (uint32_t)lane; c < ni; c += 64) p.items[at + c] = make_uint2(b, c);
     } else if (lane == 0) {
-      p.ctr[5] = 1u;
+      p.ctr[RT_CC_ITEMS_OVER] = 1u;
     }
     at += ni;
   }
@@ -1137,7 +1137,7 @@ __device__ __forceinline__ uint32_t emit_interval(const CandParams& p, int ty, i
     const uint32_t base = blk * (uint32_t)(tb * tb) + row;
     for (int tx = a; tx <= b; tx++, k++) {
       if (p.key_cap && o + k >= p.key_cap) {  // the buffers hold the previous frame's total
-        p.ctr[7] = 1u;
+        p.ctr[RT_CC_OVERFLOW] = 1u;
         continue;
       }
       const bool keep = !refine || tile_keep(p, (const float*)(p.tri + 3 * (size_t)prim), tx, ty);
@@ -1168,7 +1168,7 @@ __device__ __forceinline__ uint32_t emit_row(const CandParams& p, const Footprin
 // (tile, prim) pairs at their offsets.
 __global__ __launch_bounds__(RT_LIST_BLOCK) void emit_kernel(CandParams p) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= p.ctr[3]) return;
+  if (j >= p.ctr[RT_CC_LIST]) return;
   uint32_t o = p.off[j];
   const uint32_t n = p.off[j + 1] - o;
   if (n == 0 || n > kSmallEntries) return;  // big footprints: big_kernel
@@ -1196,17 +1196,17 @@ __global__ __launch_bounds__(RT_LIST_BLOCK) void emit_kernel(CandParams p) {
 // Pass 2b: one wave per big footprint, its tile rows over the lanes; a wave
 // prefix sum of the lanes' row counts places each lane's entries.
 __global__ __launch_bounds__(64) void big_kernel(CandParams p) {
-  // launched only when the build expects more than item_cap items (ctr[5]):
+  // launched only when the build expects more than item_cap items (ctr[RT_CC_ITEMS_OVER]):
   // read back, or -- an asynchronous build -- the same frame's earlier
   // read-back build's shape.  A shape that differs on the device (never
   // expected) means big_item_kernel was not launched: the frame is reported
-  // (ctr[7] -> RT_EHITBUF, built again with a read-back), never incomplete.
-  if (!p.ctr[5]) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) p.ctr[7] = 1u;
+  // (ctr[RT_CC_OVERFLOW] -> RT_EHITBUF, built again with a read-back), never incomplete.
+  if (!p.ctr[RT_CC_ITEMS_OVER]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) p.ctr[RT_CC_OVERFLOW] = 1u;
     return;
   }
   const int lane = threadIdx.x;
-  const uint32_t nbig = p.ctr[2];
+  const uint32_t nbig = p.ctr[RT_CC_BIG];
   for (uint32_t b = blockIdx.x; b < nbig; b += gridDim.x) {
     const uint32_t j = p.big[b], prim = p.list[j];
     const Footprint fp = p.fp[j];
@@ -1249,8 +1249,8 @@ __device__ __forceinline__ int kth_rank_col(const CandParams& p, int x0, int x1,
 // LDS.  Same (tile, prim) set as big_kernel; the sort orders it.
 // One workgroup per item.  CHECK (an asynchronous build: its grid is the
 // same frame's read-back build's) reads the item count and the over-cap flag
-// on the device: an over-cap flag (ctr[5]) the launch did not expect, or a
-// count the grid does not cover -- never expected -- sets ctr[7], so the
+// on the device: an over-cap flag (ctr[RT_CC_ITEMS_OVER]) the launch did not expect, or a
+// count the grid does not cover -- never expected -- sets ctr[RT_CC_OVERFLOW], so the
 // frame is reported rather than incomplete.  (The checks cost 16-18 VGPRs -- 4 waves
 // per SIMD instead of 5 -- so the read-back build's launch, whose grid is
 // the exact count, goes without them; a grid-stride loop over the items held
@@ -1263,12 +1263,12 @@ __global__ __launch_bounds__(64) void big_item_kernel(CandParams p) {
   __shared__ int rty[64];
   const int lane = threadIdx.x;
   if (CHECK) {
-    if (p.ctr[5]) {  // more items than item_cap after all: big_kernel was not launched (as big_kernel)
-      if (blockIdx.x == 0 && lane == 0) p.ctr[7] = 1u;
+    if (p.ctr[RT_CC_ITEMS_OVER]) {  // more items than item_cap after all: big_kernel was not launched (as big_kernel)
+      if (blockIdx.x == 0 && lane == 0) p.ctr[RT_CC_OVERFLOW] = 1u;
       return;
     }
     const uint32_t n_items = p.wave_base[kBigWaves];
-    if (blockIdx.x == 0 && lane == 0 && n_items > gridDim.x) p.ctr[7] = 1u;
+    if (blockIdx.x == 0 && lane == 0 && n_items > gridDim.x) p.ctr[RT_CC_OVERFLOW] = 1u;
     if (blockIdx.x >= n_items) return;
   }
   const uint2 it = p.items[blockIdx.x];
@@ -1277,7 +1277,7 @@ __global__ __launch_bounds__(64) void big_item_kernel(CandParams p) {
   const uint32_t c0 = it.y << p.chunk_shift;
   uint32_t c1 = c0 + (1u << p.chunk_shift) < total ? c0 + (1u << p.chunk_shift) : total;
   if (CHECK && base + c1 > p.key_cap) {  // entries past the buffers: not written, the frame reported
-    if (lane == 0) p.ctr[7] = 1u;
+    if (lane == 0) p.ctr[RT_CC_OVERFLOW] = 1u;
     c1 = p.key_cap > base ? p.key_cap - base : 0u;
   }
   const Footprint fp = p.fp[j];
@@ -1346,7 +1346,7 @@ __device__ __forceinline__ void refine_item(const CandParams& p, uint32_t item);
 #endif
 template <bool CHECK>
 __global__ __launch_bounds__(64, RT_REFINE_WAVES) void refine_kernel(CandParams p) {
-  if (CHECK && (p.ctr[5] || blockIdx.x >= p.wave_base[kBigWaves])) return;
+  if (CHECK && (p.ctr[RT_CC_ITEMS_OVER] || blockIdx.x >= p.wave_base[kBigWaves])) return;
   refine_item(p, blockIdx.x);
 }
 
@@ -1373,7 +1373,7 @@ __device__ __forceinline__ void refine_item(const CandParams& p, uint32_t item) 
     // re-read the LDS inputs per entry instead of holding them live across
     // the loop (a compiler memory barrier; 161 -> 80 VGPRs)
     __asm__ volatile("" ::: "memory");
-    if (p.key_cap && base + e >= p.key_cap) break;  // not written (ctr[7] is set)
+    if (p.key_cap && base + e >= p.key_cap) break;  // not written (ctr[RT_CC_OVERFLOW] is set)
     int tx, ty;
     rt_tile_xy(p.keys[base + e], (uint32_t)p.rank, (uint32_t)p.nranks, (uint32_t)p.blocks_x, (uint32_t)p.tb, &tx, &ty);
     if (!tile_keep(tf, tt, tx, ty)) p.keys[base + e] = p.drop_key;
@@ -1399,9 +1399,9 @@ __global__ __launch_bounds__(256) void prim_leaf_kernel(const float4* node, uint
 __global__ __launch_bounds__(256) void bounds_kernel(const uint32_t* keys, uint32_t n, uint32_t* start,
                                                      uint32_t ntiles, uint32_t* snap) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  // an asynchronous build's counters ctr[0 .. 7] -> ctr[16 .. 23] for
+  // an asynchronous build's counters -> the block's snapshot region for
   // rt_hip_stats, after every pass that may set its overflow flag
-  if (snap && t < 8u) snap[16 + t] = snap[t];
+  if (snap && t < RT_CC_BUILD_WORDS) snap[RT_CAND_CTR_SNAPSHOT + t] = snap[t];
   if (t > ntiles) return;
   uint32_t lo = 0, hi = n;
   while (lo < hi) {
@@ -1506,7 +1506,7 @@ __global__ __launch_bounds__(64) void part_scatter_kernel(const uint32_t* keys, 
     if (w == 0) start[d] = base[d];
   }
   // the build's counters beside the starts: the host reads both in one copy
-  if (w == 0 && lane < 8) start[nranks + 1 + lane] = ctr[lane];
+  if (w == 0 && lane < (int)RT_CC_BUILD_WORDS) start[rt_rstart_ctr(nranks) + lane] = ctr[lane];
   __syncthreads();
   const uint32_t e0 = w * kPartChunk, e1 = e0 + kPartChunk < n ? e0 + kPartChunk : n;
   const uint64_t lt = (1ull << lane) - 1ull;
@@ -1554,7 +1554,7 @@ __global__ __launch_bounds__(64) void part_scatter_kernel(const uint32_t* keys, 
 // kPartChunk): compact_count_kernel -> cnt[w] -> exclusive scan (off, off[nw]
 // = the kept total) -> compact_scatter_kernel writes the kept entries in
 // order at off[w] + their rank in the wave; past cap they are not written
-// and ctr7 is set (the host sized cap from the same frame's earlier build).
+// and over_flag is set (the host sized cap from the same frame's earlier build).
 __global__ __launch_bounds__(64) void compact_count_kernel(const uint32_t* keys, uint32_t n, uint32_t drop_key,
                                                            uint32_t* cnt, const uint32_t* n_dev) {
   const int lane = threadIdx.x;
@@ -1573,7 +1573,7 @@ __global__ __launch_bounds__(64) void compact_count_kernel(const uint32_t* keys,
 
 __global__ __launch_bounds__(64) void compact_scatter_kernel(const uint32_t* keys, const uint32_t* vals, uint32_t n,
                                                              uint32_t drop_key, const uint32_t* off, uint32_t cap,
-                                                             uint32_t* keys_out, uint32_t* vals_out, uint32_t* ctr7,
+                                                             uint32_t* keys_out, uint32_t* vals_out, uint32_t* over_flag,
                                                              const uint32_t* n_dev) {
   const int lane = threadIdx.x;
   const uint32_t e0 = blockIdx.x * kPartChunk;
@@ -1601,7 +1601,7 @@ __global__ __launch_bounds__(64) void compact_scatter_kernel(const uint32_t* key
         keys_out[pos] = k[t];
         vals_out[pos] = v[t];
       } else {
-        *ctr7 = 1u;
+        *over_flag = 1u;
       }
     }
     base += (uint32_t)__popcll(m);
@@ -1721,7 +1721,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_sums_kernel(const uint32_t*
 // SCATTER (the fast path's flags over the build's slice, CandParams p): the
 // exclusive prefix of a flagged prim is its place in the compact list, which
 // this pass writes directly (list[o] = prim), and the scan's last value is
-// the list length (ctr[3]) -- no offsets array, no scatter launch.
+// the list length (ctr[RT_CC_LIST]) -- no offsets array, no scatter launch.
 template <bool SCATTER>
 __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(const uint32_t* __restrict__ in, uint32_t* out,
                                                                   uint32_t nmax, const uint32_t* n_dev,
@@ -1760,7 +1760,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_apply_kernel(const uint32_t
       if (i >= n1) break;
       const uint32_t o = v[t * (kScanPer + 1) + k];
       if (i == n1 - 1u) {
-        p.ctr[3] = o;  // list length (the scan's last input is 0)
+        p.ctr[RT_CC_LIST] = o;  // list length (the scan's last input is 0)
       } else if ((flags >> k) & 1u) {
         p.list[o] = slice_prim(p, i);
       }
@@ -2109,7 +2109,7 @@ extern "C" size_t rt_cand_footprint_bytes(void) { return sizeof(rtc::Footprint);
 extern "C" hipError_t rt_cand_quick(const CandParams* p, hipStream_t s) {
   const uint32_t len = p->prim1 - p->prim0;
   if (len == 0) {  // no quick_kernel to zero the counters and the scan's last input
-    hipError_t e = hipMemsetAsync(p->ctr, 0, 8 * sizeof(uint32_t), s);
+    hipError_t e = hipMemsetAsync(p->ctr, 0, RT_CC_BUILD_WORDS * sizeof(uint32_t), s);
     return e != hipSuccess ? e : hipMemsetAsync(p->visits, 0, sizeof(uint32_t), s);
   }
   hipLaunchKernelGGL(rtc::quick_kernel, dim3((len + RT_LIST_BLOCK - 1) / RT_LIST_BLOCK), dim3(RT_LIST_BLOCK), 0, s, *p);
@@ -2165,7 +2165,7 @@ extern "C" hipError_t rt_cand_big_items(const CandParams* p, uint32_t nitems, in
   return hipGetLastError();
 }
 
-// entries [ctr[6], n) of keys (the buffers' unused tail in an asynchronous
+// entries [ctr[RT_CC_TOTAL], n) of keys (the buffers' unused tail in an asynchronous
 // build, sized from the previous frame) get `key`: they sort after every tile
 __global__ __launch_bounds__(256) void fill_tail_kernel(uint32_t* keys, const uint32_t* total, uint32_t n,
                                                         uint32_t key) {
@@ -2263,7 +2263,7 @@ extern "C" hipError_t rt_cand_route_globals(const uint32_t* global, uint32_t ngl
 
 extern "C" hipError_t rt_cand_compact(const uint32_t* keys, const uint32_t* vals, uint32_t n, const uint32_t* n_dev,
                                       uint32_t drop_key, uint32_t cap, uint32_t* cnt, uint32_t* off, void* tmp,
-                                      size_t* tmp_bytes, uint32_t* keys_out, uint32_t* vals_out, uint32_t* ctr7,
+                                      size_t* tmp_bytes, uint32_t* keys_out, uint32_t* vals_out, uint32_t* over_flag,
                                       hipStream_t s) {
   const uint32_t nw = rt_cand_part_waves(n);
   if (!tmp) return rt_cand_scan(cnt, off, nw, nullptr, tmp_bytes, s);
@@ -2272,7 +2272,7 @@ extern "C" hipError_t rt_cand_compact(const uint32_t* keys, const uint32_t* vals
   hipError_t e = rt_cand_scan(cnt, off, nw, tmp, tmp_bytes, s);  // off[nw] = the kept entries
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(rtc::compact_scatter_kernel, dim3(nw), dim3(64), 0, s, keys, vals, n, drop_key, off, cap,
-                     keys_out, vals_out, ctr7, n_dev);
+                     keys_out, vals_out, over_flag, n_dev);
   return hipGetLastError();
 }
 

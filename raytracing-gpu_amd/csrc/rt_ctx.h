@@ -63,11 +63,10 @@ extern "C" {
 
 // per-frame counters (one allocation, rt_hip_ctx::d_counter): 8 item-stream
 // counters 128 B apart, the stats, RT_HIT_REGIONS hit-record and as many
-// shade-chunk counters 32 words apart
+// shade-chunk counters RT_HIT_STRIDE words apart
 static constexpr size_t kItemCounterBytes = 8 * 128;
-static_assert(RT_NSTATS <= RT_STAT_STRIDE, "stat copies overlap");
 static constexpr size_t kStatBytes = RT_STAT_SETS * RT_STAT_STRIDE * sizeof(unsigned long long);
-static constexpr size_t kHitCounterBytes = 2 * RT_HIT_REGIONS * 32 * sizeof(uint32_t);
+static constexpr size_t kHitCounterBytes = 2 * RT_HIT_REGIONS * RT_HIT_STRIDE * sizeof(uint32_t);
 static constexpr size_t kCostBytes = 64;  // the trace's item-clock sum (KParams::cost_sum)
 static constexpr size_t kFrameCounterBytes =
     kItemCounterBytes + kStatBytes + kHitCounterBytes + kCostBytes;
@@ -182,7 +181,7 @@ struct rt_hip_ctx {
 #endif
   int cand_refine = RT_CAND_REFINE_DEFAULT;
   // view: the device word holding the last built lists' entries with a tile
-  // (d_cand_start[ntiles], or its saved copy d_cand_ctr[8])
+  // (d_cand_start[ntiles], or its saved copy d_cand_ctr[RT_CAND_CTR_SAVED_VALID])
   const uint32_t* d_cand_valid = nullptr;
   double bound_scale = 1.0;  // 1 = the proven float-MT error bound (tools/mt_bound.py)
   float4* d_tri_prim = nullptr;  // view: prim-order records, d_tri (FLAT) or d_tri_prim_own
@@ -200,7 +199,7 @@ struct rt_hip_ctx {
   DevBuf<uint32_t> d_cand_vals;    // entries (prim), emit order
   DevBuf<uint32_t> d_cand_global;  // nprim
   DevBuf<uint32_t> d_cand_big;     // nprim
-  DevBuf<uint32_t> d_cand_ctr;     // 32: [0..7] the build's counters, [8] a saved valid count, [16..23] the last asynchronous build's
+  DevBuf<uint32_t> d_cand_ctr;     // RT_CAND_CTR_BLOCK words (rt_counters.h)
   DevBuf<float> d_cand_skip;       // nprim
   DevBuf<uint32_t> d_cand_big_lane;  // kBigLaneCap x 64 lane subtotals of big footprints
   DevBuf<uint2> d_cand_items;        // kItemCap big-emission work items
@@ -212,7 +211,7 @@ struct rt_hip_ctx {
   DevBuf<uint32_t> d_cand;
   DevBuf<uint32_t> d_order;        // 3 x (ntiles + 1): heavy flags, their scan, the work order
   DevBuf<void> d_scan_tmp;
-  PinnedBuf<uint32_t> h_cand;  // pinned: a read-back build's ctr[0..7] (rt_cand.h CandParams::ctr)
+  PinnedBuf<uint32_t> h_cand;  // pinned: a read-back build's RT_CC_BUILD_WORDS counters (rt_counters.h RtCandCtr)
   // asynchronous per-rank builds (no host read-back in the render path): the
   // entry buffers are sized from an earlier frame's total, read back without
   // waiting when its build has finished
@@ -221,7 +220,7 @@ struct rt_hip_ctx {
   // late read-back of a build's kept count and counters (h_kept, ev_kept)
   ListForecast forecast;
   ListShape pknown;  // the sizes of the last read-back produce (rt_hip_cand_produce) and its frame
-  PinnedBuf<uint32_t> h_kept;  // pinned: [0] the kept count, [1..8] an asynchronous build's counters ctr[0..7]
+  PinnedBuf<uint32_t> h_kept;  // pinned: RT_KEPT_WORDS, the kept count and an asynchronous build's counters
   hipEvent_t ev_kept = nullptr;
   // the frame (camera frame, rank, nranks) whose trace last recorded its
   // per-item clocks (d_item_cost, their sum in the frame counters) and its
@@ -236,7 +235,7 @@ struct rt_hip_ctx {
   uint32_t send_n = 0;          // entries of the last produce
   DevBuf<uint32_t> d_part;    // the partition's per-wave rank counts and their scan
   DevBuf<uint32_t> d_rstart;  // nranks + 1 first entries per destination
-  PinnedBuf<uint32_t> h_rstart;  // pinned copy
+  PinnedBuf<uint32_t> h_rstart;  // pinned copy, then the build's counters (rt_rstart_words)
   KParams ext{};                // the consumed lists' kernel parameters (views into the entry, offset and order buffers)
   int ext_ready = 0, ext_rank = -1, ext_nranks = 0;
   rt_frame ext_frame{};         // the frame they were built for (compared bytewise)

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "rt_counters.h"
 #include "rt_hip.h"
 
 // The sizes of one list build, which are deterministic for its (camera
@@ -32,12 +33,14 @@ struct ListShape {
     rank = r;
     nranks = n;
   }
-  // a build's counters ctr[0..7] (rt_cand.h CandParams::ctr); [7]: it outgrew the sizes it was given
-  void set_sizes(const uint32_t ctr[8]) {
-    total = ctr[6], nglobal = ctr[1], nbig = ctr[2], nitems = ctr[4], over = ctr[5];
+  // a build's counters (rt_counters.h RtCandCtr); RT_CC_OVERFLOW: it outgrew the sizes it was given
+  void set_sizes(const uint32_t ctr[RT_CC_BUILD_WORDS]) {
+    total = ctr[RT_CC_TOTAL], nglobal = ctr[RT_CC_GLOBAL], nbig = ctr[RT_CC_BIG];
+    nitems = ctr[RT_CC_ITEMS], over = ctr[RT_CC_ITEMS_OVER];
   }
-  bool same_sizes(const uint32_t ctr[8]) const {
-    return !ctr[7] && total == ctr[6] && nglobal == ctr[1] && nbig == ctr[2] && nitems == ctr[4] && over == ctr[5];
+  bool same_sizes(const uint32_t ctr[RT_CC_BUILD_WORDS]) const {
+    return !ctr[RT_CC_OVERFLOW] && total == ctr[RT_CC_TOTAL] && nglobal == ctr[RT_CC_GLOBAL] &&
+           nbig == ctr[RT_CC_BIG] && nitems == ctr[RT_CC_ITEMS] && over == ctr[RT_CC_ITEMS_OVER];
   }
 };
 
@@ -46,7 +49,7 @@ struct ListShape {
 // deterministic -- and, with headroom, for a new camera of the same size and
 // rank split (an animation's next frame, a panned view): the last build's
 // sizes + 1/4 size the buffers and launches, every kernel checks its counts
-// on the device, and a frame past them is reported (RT_EHITBUF via ctr[7],
+// on the device, and a frame past them is reported (RT_EHITBUF via ctr[RT_CC_OVERFLOW],
 // rt_hip_stats / the frame check) and built again with a read-back.  The
 // first frame of a size or split, the compatibility mode and cand_verify's
 // rebuild (every footprint kept) read their sizes back.
@@ -63,7 +66,7 @@ struct ListPlan {
 // more short host wait instead of sorting the dropped entries (sorting them
 // all measured lists 1.96 vs 1.83 / 1.85 ms on C5, profiles/r08_compact/).
 // For a new camera the last frame's kept count + 1/16: the scatter writes the
-// unused tail as dropped, and a count past it sets ctr[7].
+// unused tail as dropped, and a count past it sets ctr[RT_CC_OVERFLOW].
 struct ListCompaction {
   bool known = false;  // to `cap` entries, from an earlier build's kept count
   bool fresh = false;  // to the build's total; the caller reads the kept count back (record_kept)
@@ -94,11 +97,11 @@ struct ListForecast {
     kept_pending = snap_pending = 0;
   }
 
-  // The last estimated-shape build's counters ctr[0..7] have arrived: the
-  // next estimate starts from them
-  void absorb_snapshot(const uint32_t ctr[8]) {
+  // The last estimated-shape build's counters have arrived: the next
+  // estimate starts from them
+  void absorb_snapshot(const uint32_t ctr[RT_CC_BUILD_WORDS]) {
     if (!snap_pending) return;
-    if (ctr[7]) {  // that frame outgrew its estimate (reported): the next build reads back
+    if (ctr[RT_CC_OVERFLOW]) {  // that frame outgrew its estimate (reported): the next build reads back
       known.valid = kept_for.valid = 0;
       kept_pending = 0;
     } else if (known.valid) {

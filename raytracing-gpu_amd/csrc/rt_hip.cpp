@@ -674,7 +674,7 @@ static int render_buffers(rt_hip_ctx* c, KParams& p) {
   p.hit_prev = c->d_hit_prev;
   p.hit_term = c->d_hit_term;
   p.hit_count = c->d_hit_count;
-  p.shade_counter = c->d_hit_count + RT_HIT_REGIONS * 32;
+  p.shade_counter = c->d_hit_count + RT_HIT_REGIONS * RT_HIT_STRIDE;
   p.hit_cap = (uint32_t)c->hit_cap();
   p.last = c->d_last;
   if (c->count_work) {  // per-item clocks of the instrumented pass (rt_hip_tile_cycles)
@@ -833,7 +833,8 @@ static int render_launch(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
     HIP_TRY(hipMemsetAsync(c->d_frame_check, 0, 4 * sizeof(unsigned long long), s));
   }
   p.frame_check = c->d_frame_check;
-  p.list_flag = c->last_async ? c->d_cand_ctr + 16 + 7 : nullptr;  // bounds_kernel's snapshot of ctr[7]
+  // (bounds_kernel's copy of the build's counters)
+  p.list_flag = c->last_async ? c->d_cand_ctr + RT_CAND_CTR_SNAPSHOT + RT_CC_OVERFLOW : nullptr;
   HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s));  // item streams, stats, record counters
   if (c->timing) HIP_TRY(hipEventRecord(ev[1], s));
   HIP_TRY(rt_launch_trace(&p, k.dacc, c->count_work, k.tpol, k.gt, s));
@@ -877,14 +878,15 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   if (!c || !out) return rt_set_error(RT_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(c->device));
   unsigned long long hs[RT_STAT_SETS * RT_STAT_STRIDE], h[RT_NSTATS];
-  uint32_t hc[RT_HIT_REGIONS * 32];
+  uint32_t hc[RT_HIT_REGIONS * RT_HIT_STRIDE];
   hipStream_t s = c->last_stream ? c->last_stream : c->stream;
   HIP_TRY(hipMemcpyAsync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(hc, c->d_hit_count, sizeof hc, hipMemcpyDeviceToHost, s));
-  uint32_t valid = 0, actr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t valid = 0, actr[RT_CC_BUILD_WORDS] = {};
   if (c->d_cand_valid) HIP_TRY(hipMemcpyAsync(&valid, c->d_cand_valid, sizeof valid, hipMemcpyDeviceToHost, s));
   const int was_async = c->last_async;
-  if (was_async) HIP_TRY(hipMemcpyAsync(actr, c->d_cand_ctr + 16, sizeof actr, hipMemcpyDeviceToHost, s));
+  if (was_async)
+    HIP_TRY(hipMemcpyAsync(actr, c->d_cand_ctr + RT_CAND_CTR_SNAPSHOT, sizeof actr, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (c->d_cand_valid) {
     c->cand_entries = valid;
@@ -892,10 +894,10 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   }
   if (was_async) {
     c->last_async = 0;
-    c->cand_global = actr[1];
-    if (actr[7]) {  // never expected (the same frame's lists): reported, and the next build reads back
+    c->cand_global = actr[RT_CC_GLOBAL];
+    if (actr[RT_CC_OVERFLOW]) {  // never expected (the same frame's lists): reported, and the next build reads back
       lists_changed(c);
-      return rt_set_error(RT_EHITBUF, "%u candidate-list entries, %u expected: render again", actr[6],
+      return rt_set_error(RT_EHITBUF, "%u candidate-list entries, %u expected: render again", actr[RT_CC_TOTAL],
                           c->forecast.known.total);
     }
   }
@@ -906,34 +908,12 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   size_t need = 0;
   unsigned long long records = 0;
   for (int x = 0; x < RT_HIT_REGIONS; x++) {
-    need = hc[32 * x] > need ? hc[32 * x] : need;
-    records += hc[32 * x];
+    need = hc[RT_HIT_STRIDE * x] > need ? hc[RT_HIT_STRIDE * x] : need;
+    records += hc[RT_HIT_STRIDE * x];
   }
   std::memset(out, 0, sizeof *out);
-  out->closest = h[0];
-  out->shadow = h[1];
-  out->pixels = h[2];
-  out->camera = 4 * h[2];
-  out->node_visits = h[3];
-  out->tri_tests = h[4];
-  out->depth_overflow = h[5];
-  out->zero_normal = h[6];
-  out->hits = h[7];
-  out->closest_node_lanes = h[8];
-  out->closest_tri_lanes = h[9];
-  out->shadow_node_lanes = h[10];
-  out->shadow_tri_lanes = h[11];
-  out->cycles_camera = h[12];
-  out->cycles_cand = h[13];
-  out->cycles_secondary = h[14];
-  out->cycles_shadow = h[15];
-  out->cycles_shadow_directional = h[16];
-  out->stack_spills = h[17];
-  out->shadow_zero_risk = h[18];
-  out->shadow_node_visits = h[19];
-  out->shadow_tri_tests = h[20];
-  out->shadow_unproven = h[21];
-  out->closest_unproven = h[22];
+  for (int k = 0; k < RT_NSTATS; k++) out->*rt_stat_member[k] = h[k];
+  out->camera = 4 * h[RT_ST_PIXELS];
   out->hit_records = records;
   out->cand_prims = c->cand_prims;
   out->cand_entries = c->cand_entries;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_counters.h"
 #include "rt_device.h"
 #include "rt_lightbuf.h"
 
@@ -16,20 +17,14 @@
 // cpu/rt recurses while coef >= 0.01 (cpu/raytracer.c:19-34), which is
 // unbounded for mirrors of Nr >= 1; paths of Nr < 1 end long before this
 #define RT_MAX_BOUNCES 16384
-#define RT_NSTATS 23
-// the counters are kept in RT_STAT_SETS copies RT_STAT_STRIDE words apart,
-// wave b adding to copy b % 8 (its XCD's): every wave of a launch flushes
-// its counters with a few 64-bit atomics, and on a small frame (C1: 4,096
-// waves of one work item each) one copy queued them for most of the kernel;
-// rt_hip_stats sums the copies
-#define RT_STAT_SETS 8
-#define RT_STAT_STRIDE 32
 // per-lane global overflow area of the traversal stack (entries beyond LDS)
 #define RT_SPILL_STACK 112
 // hit records (the wavefront split, rt_render.hip): 8 regions, one per
 // item stream, each with its own append counter; a record index is
-// region | (slot << 3), RT_NO_REC = none
+// region | (slot << 3), RT_NO_REC = none.  The regions' counters (hit_count,
+// shade_counter) lie RT_HIT_STRIDE words apart, each in its own cache line
 #define RT_HIT_REGIONS 8
+#define RT_HIT_STRIDE 32
 #define RT_NO_REC 0xffffffffu
 // occupancy target of the render kernels' launch bounds (waves per SIMD).
 // The kernels need 123 VGPRs and 9.7 KB of LDS, so they still run 4 waves
@@ -127,10 +122,10 @@ struct KParams {
   float4* hit;                  // RT_HIT_REGIONS x hit_cap records: P.xyz N.x | N.yz coef obj
   uint32_t* hit_prev;           // per record: the path's previous record (RT_NO_REC)
   float4* hit_term;             // per record: color_mul(apply_light(...), coef), rgb
-  uint32_t* hit_count;          // RT_HIT_REGIONS append counters, 32 words apart
+  uint32_t* hit_count;          // RT_HIT_REGIONS append counters, RT_HIT_STRIDE words apart
   uint32_t hit_cap;             // records per region
   uint32_t* last;               // per (item, lane): the path's deepest record (RT_NO_REC)
-  uint32_t* shade_counter;      // RT_HIT_REGIONS chunk counters of shade_kernel, 32 words apart
+  uint32_t* shade_counter;      // RT_HIT_REGIONS chunk counters of shade_kernel, RT_HIT_STRIDE apart
   // shadow verification (rt_hip_verify_shadows; NULL / 0 in renders): the
   // shade pass writes each shaded record's unshadowed-light mask (lights
   // 0..31) and shades only every shade_stride-th record of each region
@@ -156,7 +151,7 @@ struct KParams {
   uint32_t* oob_count;
   uint32_t oob_cap;
   uint32_t* tile_counter;       // 8 item-stream counters, 32 words apart; zeroed before launch
-  unsigned long long* stats;    // RT_NSTATS counters, zeroed before launch
+  unsigned long long* stats;    // RT_NSTATS counters (rt_counters.h RtStat), zeroed before launch
   uint2* spill;                 // grid*64 lanes x RT_SPILL_STACK stack entries
   rt::f3 scene_c;               // scene box centre
   float scene_cmag;             // max-norm of scene_c
@@ -186,8 +181,8 @@ struct KParams {
   // (RT_FRAME_*), frame_check[1] += 1 frame, [2] / [3] += its closest-hit /
   // shadow queries -- sticky across frames until rt_hip_frame_check reads
   // them, so a timed loop of many frames is checked and counted as a whole.
-  // list_flag: the frame's asynchronous list build's overflow flag (ctr[7]),
-  // or NULL
+  // list_flag: the frame's asynchronous list build's overflow flag (the
+  // snapshot's RT_CC_OVERFLOW), or NULL
   unsigned long long* frame_check;
   const uint32_t* list_flag;
   // G-buffer capture (RT_POLICY_GBUFFER; NULL otherwise), per (item, lane) like
@@ -200,11 +195,7 @@ struct KParams {
   // of the record's stored mask hit_lit (csrc/rt_relight.h).  Appended too
   uint32_t relight_dirty;
 };
-#define RT_FRAME_HITBUF 1u     // hit records past a region's capacity
-#define RT_FRAME_DEPTH 2u      // bounce limit or traversal stack overflow
-#define RT_FRAME_ZERO 4u       // zero interpolated normal (closest or shadow)
-#define RT_FRAME_UNPROVEN 8u   // shadow queries the exact mode could not decide
-#define RT_FRAME_LISTS 16u     // asynchronous list build overflow
+// (the bits of frame_check[0], RT_FRAME_*: rt_counters.h)
 
 // The three launches of one render (policy = RT_POLICY_*, octree only):
 // trace (closest hits -> hit records), shade (shadow queries + Phong per

@@ -53,6 +53,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "rt_counters.h"
 #include "rt_lightbuf.h"
 
 namespace rtl {
@@ -87,7 +88,7 @@ struct BP {
   unsigned long long* keys;
   uint32_t* vals;
   uint32_t* big;
-  uint32_t* ctr;  // [0] big prims, [1] global prims, [2] never accepted, [3] band, [4] emission overflow
+  uint32_t* ctr;  // RT_LBC_WORDS counters (rt_counters.h RtLbCtr)
   uint32_t* global;
 };
 
@@ -694,7 +695,7 @@ RTL_FN inline uint32_t foot_rows(const BP& p, const Foot& f) {
 
 // entries of row `row`; with emit, written from `at` on, never at or past
 // `lim` (the prim's own range: a count/emission mismatch is flagged in
-// ctr[4], not written out of bounds)
+// ctr[RT_LBC_OVERFLOW], not written out of bounds)
 template <bool EMIT>
 RTL_FN inline uint32_t row_entries(const BP& p, const Foot& f, uint32_t prim, uint32_t row, uint64_t at,
                                        uint64_t lim) {
@@ -710,7 +711,7 @@ RTL_FN inline uint32_t row_entries(const BP& p, const Foot& f, uint32_t prim, ui
       if (cell_overlaps(p, f, q, x, y)) {
         if constexpr (EMIT) {
           if (at + c >= lim) {
-            p.ctr[4] = 1u;
+            p.ctr[RT_LBC_OVERFLOW] = 1u;
             return c;
           }
           p.keys[at + c] = ((unsigned long long)cell_index(p, f, q, x, y) << 32) | orderable(cell_key(p, f, x, y));
@@ -729,7 +730,7 @@ RTL_FN inline uint32_t row_entries(const BP& p, const Foot& f, uint32_t prim, ui
     for (int x = xa; x <= xb; x++) {
       const uint64_t i = at + (uint64_t)(x - xa);
       if (i >= lim) {
-        p.ctr[4] = 1u;
+        p.ctr[RT_LBC_OVERFLOW] = 1u;
         break;
       }
       p.keys[i] = ((unsigned long long)(face * p.n * p.n + y * p.n + (uint32_t)x) << 32) | kb;
@@ -805,12 +806,12 @@ __global__ __launch_bounds__(256) void count_kernel(BP p) {
   footprint(p, prim, f);
   uint32_t c = 0;
   if (f.never) {
-    atomicAdd(p.ctr + 2, 1u);
+    atomicAdd(p.ctr + RT_LBC_NEVER, 1u);
   } else if (f.global) {
-    p.global[atomicAdd(p.ctr + 1, 1u)] = prim;
+    p.global[atomicAdd(p.ctr + RT_LBC_GLOBAL, 1u)] = prim;
   } else if (foot_is_big(p, f)) {
-    p.big[atomicAdd(p.ctr, 1u)] = prim;  // counted and emitted row-wise by a workgroup
-    if (f.band) atomicAdd(p.ctr + 3, 1u);
+    p.big[atomicAdd(p.ctr + RT_LBC_BIG, 1u)] = prim;  // counted and emitted row-wise by a workgroup
+    if (f.band) atomicAdd(p.ctr + RT_LBC_BAND, 1u);
   } else {
     const uint32_t rows = foot_rows(p, f);
     for (uint32_t r = 0; r < rows; r++) c += row_entries<false>(p, f, prim, r, 0, 0);
@@ -832,7 +833,7 @@ __device__ inline uint32_t block_sum(uint32_t v, uint32_t* red) {
 // one workgroup per big footprint: its rows over the threads
 __global__ __launch_bounds__(256) void big_count_kernel(BP p) {
   __shared__ uint32_t red[kBlock / 64];
-  for (uint32_t b = blockIdx.x; b < p.ctr[0]; b += gridDim.x) {
+  for (uint32_t b = blockIdx.x; b < p.ctr[RT_LBC_BIG]; b += gridDim.x) {
     const uint32_t prim = p.big[b];
     Foot f;
     footprint(p, prim, f);
@@ -862,7 +863,7 @@ __global__ __launch_bounds__(256) void emit_kernel(BP p) {
 __global__ __launch_bounds__(256) void big_emit_kernel(BP p) {
   __shared__ uint32_t wsum[kBlock / 64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (uint32_t b = blockIdx.x; b < p.ctr[0]; b += gridDim.x) {
+  for (uint32_t b = blockIdx.x; b < p.ctr[RT_LBC_BIG]; b += gridDim.x) {
     const uint32_t prim = p.big[b];
     Foot f;
     footprint(p, prim, f);
@@ -1103,16 +1104,16 @@ extern "C" int rt_lightbuf_build(const LBParams* in, RtLightBuf* out, LBDevice**
   uint32_t* v0 = nullptr;
   void* tmp = nullptr;
   size_t tb = 0;
-  uint32_t hc[5] = {0, 0, 0, 0, 0}, last_off = 0, last_cnt = 0;
+  uint32_t hc[RT_LBC_WORDS] = {}, last_off = 0, last_cnt = 0;
   const uint32_t np = in->nprim;
   const dim3 gp((np + 255) / 256), bk(256);
   LB_TRY(hipMalloc((void**)&count, ((size_t)np + 1) * sizeof(uint32_t)));
   LB_TRY(hipMalloc((void**)&off, ((size_t)np + 1) * sizeof(uint32_t)));
-  LB_TRY(hipMalloc((void**)&ctr, 5 * sizeof(uint32_t)));
+  LB_TRY(hipMalloc((void**)&ctr, RT_LBC_WORDS * sizeof(uint32_t)));
   LB_TRY(hipMalloc((void**)&big, ((size_t)np + 1) * sizeof(uint32_t)));
   LB_TRY(hipMalloc((void**)&dev->global, ((size_t)np + 1) * sizeof(uint32_t)));
   LB_TRY(hipMalloc((void**)&dev->start, (ncell + 1) * sizeof(uint32_t)));
-  LB_TRY(hipMemsetAsync(ctr, 0, 5 * sizeof(uint32_t), s));
+  LB_TRY(hipMemsetAsync(ctr, 0, RT_LBC_WORDS * sizeof(uint32_t), s));
   LB_TRY(hipMemsetAsync(count + np, 0, sizeof(uint32_t), s));
   p.count = count;
   p.off = off;
@@ -1165,9 +1166,9 @@ extern "C" int rt_lightbuf_build(const LBParams* in, RtLightBuf* out, LBDevice**
   }
   dev->entries = total;
   dev->cells = ncell;
-  dev->nglobal = hc[1];
-  dev->never = hc[2];
-  dev->band = hc[3];
+  dev->nglobal = hc[RT_LBC_GLOBAL];
+  dev->never = hc[RT_LBC_NEVER];
+  dev->band = hc[RT_LBC_BAND];
   LB_TRY(hipMalloc((void**)&dev->prim, (total + 1) * sizeof(uint32_t)));
   LB_TRY(hipMalloc((void**)&dev->rec, (total + 1) * 3 * sizeof(float4)));
   if (total) {
@@ -1178,8 +1179,8 @@ extern "C" int rt_lightbuf_build(const LBParams* in, RtLightBuf* out, LBDevice**
     p.vals = v0;
     hipLaunchKernelGGL(emit_kernel, gp, bk, 0, s, p);
     LB_TRY(hipGetLastError());
-    if (hc[0]) {
-      hipLaunchKernelGGL(big_emit_kernel, dim3(hc[0] < 4096 ? hc[0] : 4096), bk, 0, s, p);
+    if (const uint32_t nbig = hc[RT_LBC_BIG]) {
+      hipLaunchKernelGGL(big_emit_kernel, dim3(nbig < 4096 ? nbig : 4096), bk, 0, s, p);
       LB_TRY(hipGetLastError());
     }
     int bits = 32;
@@ -1203,9 +1204,9 @@ extern "C" int rt_lightbuf_build(const LBParams* in, RtLightBuf* out, LBDevice**
   } else {
     LB_TRY(hipMemsetAsync(dev->start, 0, (ncell + 1) * sizeof(uint32_t), s));
   }
-  LB_TRY(hipMemcpyAsync(hc + 4, ctr + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  LB_TRY(hipMemcpyAsync(hc + RT_LBC_OVERFLOW, ctr + RT_LBC_OVERFLOW, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   LB_TRY(hipStreamSynchronize(s));
-  if (hc[4]) {
+  if (hc[RT_LBC_OVERFLOW]) {
     snprintf(err, errlen, "light buffer emission disagreed with its count");
     rc = -1;
     goto done;
@@ -1213,7 +1214,7 @@ extern "C" int rt_lightbuf_build(const LBParams* in, RtLightBuf* out, LBDevice**
   out->start = dev->start;
   out->rec = dev->rec;
   out->global = dev->global;
-  out->nglobal = hc[1];
+  out->nglobal = hc[RT_LBC_GLOBAL];
 done:
   (void)hipFree(count);
   (void)hipFree(off);

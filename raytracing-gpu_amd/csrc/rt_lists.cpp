@@ -138,9 +138,8 @@ static int cand_verify(rt_hip_ctx* c, const rt_frame* f, KParams kp, int compat,
   const uint32_t nt = (uint32_t)cp.ntiles_local;
   cp.refine = c->cand_refine ? 1u : 0u;
   cp.drop_key = nt;
-  uint32_t ctr[4];
-  HIP_TRY(hipMemcpy(ctr, c->d_cand_ctr, sizeof ctr, hipMemcpyDeviceToHost));
-  const uint32_t nlist = ctr[3];
+  uint32_t nlist = 0;
+  HIP_TRY(hipMemcpy(&nlist, c->d_cand_ctr + RT_CC_LIST, sizeof nlist, hipMemcpyDeviceToHost));
   std::vector<uint32_t> start(nt + 1), list(nlist + 1), pl;
   HIP_TRY(hipMemcpy(start.data(), c->d_cand_start, (nt + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
   std::vector<uint32_t> cand(start[nt] + 1);
@@ -341,11 +340,13 @@ int cand_params(const rt_frame* f, const float scene_c[3], float scene_r, float 
 
 // The last render's kept-entry count (rt_hip_stats reads it) outlives a list
 // build that overwrites the offsets it points into: saved in stream order to
-// a word no build writes (d_cand_ctr[8]).
+// a word no build writes (d_cand_ctr[RT_CAND_CTR_SAVED_VALID]).
 static int save_valid(rt_hip_ctx* c, hipStream_t s) {
-  if (!c->d_cand_valid || !c->d_cand_ctr || c->d_cand_valid == c->d_cand_ctr + 8) return RT_OK;
-  HIP_TRY(hipMemcpyAsync(c->d_cand_ctr + 8, c->d_cand_valid, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-  c->d_cand_valid = c->d_cand_ctr + 8;
+  if (!c->d_cand_valid || !c->d_cand_ctr) return RT_OK;
+  uint32_t* const saved = c->d_cand_ctr + RT_CAND_CTR_SAVED_VALID;
+  if (c->d_cand_valid == saved) return RT_OK;
+  HIP_TRY(hipMemcpyAsync(saved, c->d_cand_valid, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  c->d_cand_valid = saved;
   return RT_OK;
 }
 
@@ -367,7 +368,7 @@ static int cand_entry_buffers(rt_hip_ctx* c, size_t n) {
 static int cand_tile_buffers(rt_hip_ctx* c, size_t nt) {
   if (!c->d_cand_start.holds(nt + 1) || !c->d_order.holds(3 * (nt + 1))) {
     c->ext_ready = 0;  // the consumed lists' offsets and work order live here
-    if (c->d_cand_valid && c->d_cand_valid != c->d_cand_ctr + 8) c->d_cand_valid = nullptr;
+    if (c->d_cand_valid && c->d_cand_valid != c->d_cand_ctr + RT_CAND_CTR_SAVED_VALID) c->d_cand_valid = nullptr;
   }
   HIP_TRY(c->d_cand_start.grow(nt + 1, list_room(nt + 1)));
   HIP_TRY(c->d_order.grow(3 * (nt + 1), 3 * (nt + 1)));
@@ -434,7 +435,7 @@ static bool cand_scene_buffers(rt_hip_ctx* c, Fn&& fn) {
   const size_t np1 = (size_t)c->nprim + 1, nw = (size_t)rt_cand_big_waves() + 1;
   return fn(c->d_cand_list, np1) && fn(c->d_cand_fp, np1 * rt_cand_footprint_bytes()) &&
          fn(c->d_cand_sfp, 2 * np1) && fn(c->d_cand_visits, np1) && fn(c->d_cand_off, np1) &&
-         fn(c->d_cand_global, np1) && fn(c->d_cand_big, np1) && fn(c->d_cand_ctr, 32) &&
+         fn(c->d_cand_global, np1) && fn(c->d_cand_big, np1) && fn(c->d_cand_ctr, RT_CAND_CTR_BLOCK) &&
          fn(c->d_cand_skip, np1) && fn(c->d_cand_big_lane, (size_t)kBigLaneCap * 64) &&
          fn(c->d_cand_items, (size_t)kItemCap + 1) && fn(c->d_cand_wave_items, nw) &&
          fn(c->d_cand_wave_base, nw) && fn(c->d_scan_bsum, (size_t)rt_cand_scan_dev_tiles(c->nprim));
@@ -460,13 +461,13 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   }
   cp.node = c->d_node;
   cp.prim_leaf = c->d_prim_leaf;
-  if (!cand_scene_buffers(c, [](auto& b, size_t n) { return b.holds(n); }) || !c->h_cand.holds(8)) {
+  if (!cand_scene_buffers(c, [](auto& b, size_t n) { return b.holds(n); }) || !c->h_cand.holds(RT_CC_BUILD_WORDS)) {
     cand_scene_buffers(c, [](auto& b, size_t) { return b.reset(), true; });
     hipError_t he = hipSuccess;
     cand_scene_buffers(c, [&](auto& b, size_t n) { return (he = b.alloc(n)) == hipSuccess; });
     HIP_TRY(he);
     HIP_TRY(hipMemset(c->d_cand_wave_items, 0, c->d_cand_wave_items.cap() * sizeof(uint32_t)));  // [last] stays 0
-    HIP_TRY(c->h_cand.grow(8, 8));
+    HIP_TRY(c->h_cand.grow(RT_CC_BUILD_WORDS, RT_CC_BUILD_WORDS));
   }
   cp.list = c->d_cand_list;
   cp.fp = (rtc::Footprint*)c->d_cand_fp.get();
@@ -488,7 +489,7 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   cp.wave_base = c->d_cand_wave_base;
   cp.refine = c->cand_refine ? 1u : 0u;
   cp.drop_key = (uint32_t)cp.ntiles_local;  // sorts after the tiles (their keys are < ntiles_local)
-  // (ctr[0 .. 7] and visits[np] are zeroed by quick_kernel)
+  // (the build's counters and visits[np] are zeroed by quick_kernel)
   // (temporary storage for both scans, before the launches)
   const auto prim_scan = [&](void* tmp, size_t* tb) {
     return rt_cand_scan(c->d_cand_visits, c->d_cand_off, (uint32_t)np, tmp, tb, s);
@@ -510,14 +511,14 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
   size_t tb = c->d_scan_tmp.cap();
   HIP_TRY(wave_scan(c->d_scan_tmp, &tb));
   HIP_TRY(rt_cand_items(&cp, s));
-  // over the list's length only (ctr[3], on the device); the entry total -> ctr[6]
-  HIP_TRY(rt_cand_scan_dev(c->d_cand_visits, c->d_cand_off, (uint32_t)np, c->d_cand_ctr + 3, c->d_cand_ctr + 6,
-                           c->d_scan_bsum, s));
+  // over the list's length only (on the device); the entry total -> its counter
+  HIP_TRY(rt_cand_scan_dev(c->d_cand_visits, c->d_cand_off, (uint32_t)np, c->d_cand_ctr + RT_CC_LIST,
+                           c->d_cand_ctr + RT_CC_TOTAL, c->d_scan_bsum, s));
   if (known) {
     // no read-back: the frame's lists were built before with a read-back of
     // their sizes (deterministic for the same frame), so the buffers hold
     // them; an entry past known->total would not be written and would set
-    // ctr[7] (rt_hip_stats then reports the frame, rt_hip_cand_produce
+    // ctr[RT_CC_OVERFLOW] (rt_hip_stats then reports the frame, rt_hip_cand_produce
     // builds again: never silent).  The emission kernels read the item
     // count and the over-cap flag on the device and the render reads the
     // global prims' count there
@@ -533,20 +534,19 @@ static int cand_build(rt_hip_ctx* c, CandParams& cp, hipStream_t s, uint32_t glo
       HIP_TRY(rt_cand_big(&cp, known->nbig, s));
     else
       HIP_TRY(rt_cand_big_items(&cp, known->nitems, 1, s));
-    // (entries past the build's own total, ctr[6] -- never expected -- are
+    // (entries past the build's own total, ctr[RT_CC_TOTAL] -- never expected -- are
     // left to the caller: cand_prepare drops them before the sort, a
     // produce's partition routes them as dropped; and cand_prepare's
     // bounds_kernel snapshots the counters for rt_hip_stats)
     *total_out = known->total;  // the sort's length
-    *nglobal_out = known->nglobal;  // (the render reads the count on the device, ctr[1])
+    *nglobal_out = known->nglobal;  // (the render reads the count on the device, ctr[RT_CC_GLOBAL])
     return RT_OK;
   }
-  // one read-back of the build's sizes: ctr[1..6] (the total in [6], the
-  // items in [4])
-  HIP_TRY(hipMemcpyAsync(c->h_cand, c->d_cand_ctr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  // one read-back of the build's sizes
+  HIP_TRY(hipMemcpyAsync(c->h_cand, c->d_cand_ctr, RT_CC_BUILD_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  const uint32_t total = c->h_cand[6], nglobal = c->h_cand[1], nbig = c->h_cand[2];
-  const uint32_t nitems = c->h_cand[4], items_over = c->h_cand[5];
+  const uint32_t total = c->h_cand[RT_CC_TOTAL], nglobal = c->h_cand[RT_CC_GLOBAL], nbig = c->h_cand[RT_CC_BIG];
+  const uint32_t nitems = c->h_cand[RT_CC_ITEMS], items_over = c->h_cand[RT_CC_ITEMS_OVER];
   rc = cand_entry_buffers(c, (size_t)total + (size_t)glob_copies * nglobal);
   if (rc) return rc;
   cp.key_cap = 0;
@@ -592,7 +592,7 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   const int rank = kp->rank, nranks = kp->nranks;
   // the last estimated-shape build's counters, once their read-back is done
   const auto arrived = [&] { return c->ev_kept && hipEventQuery(c->ev_kept) == hipSuccess; };
-  if (fc.snap_pending && arrived()) fc.absorb_snapshot(c->h_kept + 1);
+  if (fc.snap_pending && arrived()) fc.absorb_snapshot(c->h_kept + RT_KEPT_CTR);
   const ListPlan plan = fc.plan(f, rank, nranks, c->async_lists, c->cand_store_fp, compat);
   const bool async = plan.async;
   ListShape built;
@@ -600,14 +600,14 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   if (rc) return rc;
   c->last_async = async ? 1 : 0;
   if (async)
-    nglobal = 0;  // on the device (ctr[1])
+    nglobal = 0;  // on the device (ctr[RT_CC_GLOBAL])
   else
     fc.record_build(built, f, rank, nranks, compat);
   rc = cand_tile_buffers(c, nt);
   if (rc) return rc;
   // the kept count of the last build of this size and split, once its
   // read-back is done
-  if (fc.kept_pending && arrived()) fc.absorb_kept(*c->h_kept);
+  if (fc.kept_pending && arrived()) fc.absorb_kept(c->h_kept[RT_KEPT_COUNT]);
   const ListCompaction compact = fc.compaction(plan, f, rank, nranks, total, c->cand_refine, c->cand_store_fp, compat);
   bool kept_now = false;
   if (compact) {
@@ -619,16 +619,17 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
     uint32_t* cnt = c->d_part;
     uint32_t* off = c->d_part + nw + 1;
     const auto compaction = [&](void* tmp, size_t* tb) {
-      return rt_cand_compact(c->d_cand_keys, c->d_cand_vals, total, c->d_cand_ctr + 6, (uint32_t)nt, compact.cap, cnt,
-                             off, tmp, tb, c->d_cand_keys2, c->d_cand, c->d_cand_ctr + 7, s);
+      return rt_cand_compact(c->d_cand_keys, c->d_cand_vals, total, c->d_cand_ctr + RT_CC_TOTAL, (uint32_t)nt,
+                             compact.cap, cnt, off, tmp, tb, c->d_cand_keys2, c->d_cand,
+                             c->d_cand_ctr + RT_CC_OVERFLOW, s);
     };
     HIP_TRY(with_tmp(c->d_scan_tmp, compaction));
     uint32_t kept = compact.cap;
     if (compact.fresh) {  // off[nw] = the kept entries
-      HIP_TRY(c->h_kept.grow(9, 9));
-      HIP_TRY(hipMemcpyAsync(c->h_kept, off + nw, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(c->h_kept.grow(RT_KEPT_WORDS, RT_KEPT_WORDS));
+      HIP_TRY(hipMemcpyAsync(c->h_kept + RT_KEPT_COUNT, off + nw, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
-      kept = *c->h_kept;
+      kept = c->h_kept[RT_KEPT_COUNT];
       if (kept > total) return rt_set_error(RT_EHIP, "compaction kept %u of %u entries", kept, total);
       fc.record_kept(kept, f, rank, nranks);
       kept_now = true;
@@ -640,7 +641,7 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
     total = kept;
   } else {
     // an asynchronous build's entries past its own total (never expected): dropped
-    if (async) HIP_TRY(rt_cand_fill_tail(c->d_cand_keys, c->d_cand_ctr + 6, total, (uint32_t)nt, s));
+    if (async) HIP_TRY(rt_cand_fill_tail(c->d_cand_keys, c->d_cand_ctr + RT_CC_TOTAL, total, (uint32_t)nt, s));
     // keys are tiles < nt, or nt for an entry the refinement dropped: nt + 1 keys
     rc = cand_sort(c, c->d_cand_keys, c->d_cand_keys2, c->d_cand_vals, c->d_cand, total, nt + 1, s);
     if (rc) return rc;
@@ -649,11 +650,13 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   // (an asynchronous build's counters snapshot for rt_hip_stats, where no build writes)
   HIP_TRY(rt_cand_bounds(c->d_cand_keys2, total, c->d_cand_start, (uint32_t)nt, async ? c->d_cand_ctr : nullptr, s));
   if (fc.wants_late_readback(plan, f, rank, nranks, c->cand_refine, compat, kept_now)) {
-    HIP_TRY(c->h_kept.grow(9, 9));
+    HIP_TRY(c->h_kept.grow(RT_KEPT_WORDS, RT_KEPT_WORDS));
     if (!c->ev_kept) HIP_TRY(hipEventCreateWithFlags(&c->ev_kept, hipEventDisableTiming));
-    HIP_TRY(hipMemcpyAsync(c->h_kept, c->d_cand_start + nt, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(c->h_kept + RT_KEPT_COUNT, c->d_cand_start + nt, sizeof(uint32_t), hipMemcpyDeviceToHost,
+                           s));
     if (plan.estimated)  // bounds_kernel's snapshot of its counters
-      HIP_TRY(hipMemcpyAsync(c->h_kept + 1, c->d_cand_ctr + 16, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(c->h_kept + RT_KEPT_CTR, c->d_cand_ctr + RT_CAND_CTR_SNAPSHOT,
+                             RT_CC_BUILD_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipEventRecord(c->ev_kept, s));
     fc.late_readback_requested(plan, f, rank, nranks);
   }
@@ -666,7 +669,7 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   kp->cand = c->d_cand;
   kp->cand_global = c->d_cand_global;
   kp->n_cand_global = nglobal;
-  kp->n_cand_global_dev = async ? c->d_cand_ctr + 1 : nullptr;
+  kp->n_cand_global_dev = async ? c->d_cand_ctr + RT_CC_GLOBAL : nullptr;
   kp->cand_skip = entry_skip;
   c->cand_entries = total;  // until rt_hip_stats reads start[nt]
   c->d_cand_valid = (c->cand_refine || async) ? c->d_cand_start + nt : nullptr;
@@ -732,8 +735,9 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
                                 c->d_cand_vals + total, s));
   const uint32_t n = total + nglobal * (uint32_t)nranks;
   // the starts, then the build's counters
-  HIP_TRY(c->d_rstart.grow((size_t)nranks + 9, (size_t)nranks + 9));
-  HIP_TRY(c->h_rstart.grow((size_t)nranks + 9, (size_t)nranks + 9));
+  const size_t nstart = rt_rstart_words(nranks);
+  HIP_TRY(c->d_rstart.grow(nstart, nstart));
+  HIP_TRY(c->h_rstart.grow(nstart, nstart));
   HIP_TRY(c->d_send.grow(3 * (size_t)n + 1, 3 * ((size_t)n + n / 4 + 1024)));
   // per-wave rank counts (rank-major) -> exclusive scan -> stable scatter
   const size_t nh = ((size_t)nranks + 1) * rt_cand_part_waves(n);
@@ -742,17 +746,17 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
   uint32_t* hoff = c->d_part + nh + 1;
   if (nh) {
     HIP_TRY(rt_cand_part_count(c->d_cand_keys, n, (uint32_t)tbits, nranks, hist, total, cp.tiles_x,
-                               rt_blocks_x(cp.tiles_x, tb), tb, cp.drop_key, async ? c->d_cand_ctr + 6 : nullptr, s));
+                               rt_blocks_x(cp.tiles_x, tb), tb, cp.drop_key,
+                               async ? c->d_cand_ctr + RT_CC_TOTAL : nullptr, s));
     const auto scan = [&](void* tmp, size_t* bytes) { return rt_cand_scan(hist, hoff, (uint32_t)(nh - 1), tmp, bytes, s); };
     HIP_TRY(with_tmp(c->d_scan_tmp, scan));
   }
   HIP_TRY(rt_cand_part_scatter(c->d_cand_keys, c->d_cand_vals, c->d_cand_skip, n, (uint32_t)tbits, nranks, hoff,
                                c->d_rstart, c->d_send, c->d_cand_ctr, s));
   // the per-rank starts and the build's counters in one read-back
-  HIP_TRY(hipMemcpyAsync(c->h_rstart, c->d_rstart, ((size_t)nranks + 9) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                         s));
+  HIP_TRY(hipMemcpyAsync(c->h_rstart, c->d_rstart, nstart * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  const uint32_t* hc = c->h_rstart + nranks + 1;  // ctr[0 .. 7]
+  const uint32_t* hc = c->h_rstart + rt_rstart_ctr(nranks);  // the build's counters
   if (async && !c->pknown.same_sizes(hc)) {
     c->pknown.valid = 0;  // not this slice's sizes after all: build it with the read-back
     return rt_hip_cand_produce(c, f, rank, nranks, counts, nglobal_out, stream);

@@ -13,23 +13,30 @@
 
 namespace rt {
 
-// The stat slots a shade pass adds to (flush_counts with shade = true; the
-// order of rt_hip_stats): 1 shadow, 10 11 15 16 the shadow queries' lane work
-// and clocks, 18 shadow_zero_risk, 19 20 their record fetches, 21
-// shadow_unproven.
-__device__ __forceinline__ bool shade_stat_slot(uint32_t k) {
-  return k == 1 || k == 10 || k == 11 || k == 15 || k == 16 || (k >= 18 && k <= 21);
+// The stat slots a shade pass adds to.  rt_counters.h's list decides them
+// (rt_stat_shade_side); this chain only has to agree with it, and is kept in
+// this shape -- the single slots, then the run as a range -- because the
+// compiler's code for relight_zero_kernel follows the shape of the expression.
+constexpr bool shade_stat_slot(uint32_t k) {
+  return k == RT_ST_SHADOW || k == RT_ST_SHADOW_NODE_LANES || k == RT_ST_SHADOW_TRI_LANES ||
+         k == RT_ST_CYCLES_SHADOW || k == RT_ST_CYCLES_SHADOW_DIRECTIONAL ||
+         (k >= RT_ST_SHADOW_ZERO_RISK && k <= RT_ST_SHADOW_UNPROVEN);
 }
+constexpr bool shade_stat_slots_agree(uint32_t k = 0) {
+  return k == RT_STAT_STRIDE || (shade_stat_slot(k) == rt_stat_shade_side(k) && shade_stat_slots_agree(k + 1));
+}
+static_assert(shade_stat_slots_agree(), "shade_stat_slot differs from the SHADE rows of RT_STAT_LIST");
 
-// One workgroup: the RT_HIT_REGIONS shade chunk counters (32 words apart) and
-// the shadow-side stat slots of every copy.  The hit-record counters, the item
+// One workgroup: the RT_HIT_REGIONS shade chunk counters (RT_HIT_STRIDE apart)
+// and the shade-side stat slots of every copy.  The hit-record counters, the item
 // streams, the trace's stats and its cost sum stay: they are the traced
 // frame's.
 template <int K = 0>
 __global__ __launch_bounds__(256) void relight_zero_kernel(KParams p) {
-  static_assert(RT_HIT_REGIONS * 32 <= 256 && RT_STAT_SETS * RT_STAT_STRIDE <= 256, "one workgroup covers both");
+  static_assert(RT_HIT_REGIONS * RT_HIT_STRIDE <= 256 && RT_STAT_SETS * RT_STAT_STRIDE <= 256,
+                "one workgroup covers both");
   const uint32_t t = threadIdx.x;
-  if (t < RT_HIT_REGIONS * 32u) p.shade_counter[t] = 0u;
+  if (t < RT_HIT_REGIONS * RT_HIT_STRIDE) p.shade_counter[t] = 0u;
   if (t < RT_STAT_SETS * RT_STAT_STRIDE && shade_stat_slot(t % RT_STAT_STRIDE)) p.stats[t] = 0ull;
 }
 
@@ -67,7 +74,7 @@ __global__ __launch_bounds__(256) void recolour_kernel(KParams p) {
   uint32_t total = 0;
 #pragma unroll
   for (int x = 0; x < RT_HIT_REGIONS; x++) {
-    const uint32_t hc = p.hit_count[32 * x];
+    const uint32_t hc = p.hit_count[RT_HIT_STRIDE * x];
     total += hc < p.hit_cap ? hc : p.hit_cap;
     end[x] = total;
   }

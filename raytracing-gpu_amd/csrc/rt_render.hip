@@ -62,12 +62,17 @@ __device__ __forceinline__ void tile_pixel(const KParams& p, uint32_t t, int lan
 // can be priced on its own (bench.py roofline).
 __device__ __forceinline__ void flush_counts(const KParams& p, const WorkCount& wc, int lane,
                                              bool shade = false) {
-  uint32_t v[RT_NSTATS] = {wc.closest, wc.shadow,   wc.pixels,      shade ? 0u : wc.nodes,
-                           shade ? 0u : wc.tris,    wc.overflow, wc.zero_normal, wc.hits,
-                           wc.cl_nodes, wc.cl_tris, wc.sh_nodes,   wc.sh_tris,
-                           wc.cy_cam,   wc.cy_cand, wc.cy_sec,     wc.cy_shadow,
-                           wc.cy_shadow_dir, wc.stack_spills, wc.zero_risk,
-                           shade ? wc.nodes : 0u, shade ? wc.tris : 0u, wc.sh_unproven, wc.cl_unproven};
+  uint32_t v[RT_NSTATS];
+  v[RT_ST_CLOSEST] = wc.closest, v[RT_ST_SHADOW] = wc.shadow, v[RT_ST_PIXELS] = wc.pixels;
+  v[RT_ST_NODE_VISITS] = shade ? 0u : wc.nodes, v[RT_ST_TRI_TESTS] = shade ? 0u : wc.tris;
+  v[RT_ST_DEPTH_OVERFLOW] = wc.overflow, v[RT_ST_ZERO_NORMAL] = wc.zero_normal, v[RT_ST_HITS] = wc.hits;
+  v[RT_ST_CLOSEST_NODE_LANES] = wc.cl_nodes, v[RT_ST_CLOSEST_TRI_LANES] = wc.cl_tris;
+  v[RT_ST_SHADOW_NODE_LANES] = wc.sh_nodes, v[RT_ST_SHADOW_TRI_LANES] = wc.sh_tris;
+  v[RT_ST_CYCLES_CAMERA] = wc.cy_cam, v[RT_ST_CYCLES_CAND] = wc.cy_cand, v[RT_ST_CYCLES_SECONDARY] = wc.cy_sec;
+  v[RT_ST_CYCLES_SHADOW] = wc.cy_shadow, v[RT_ST_CYCLES_SHADOW_DIRECTIONAL] = wc.cy_shadow_dir;
+  v[RT_ST_STACK_SPILLS] = wc.stack_spills, v[RT_ST_SHADOW_ZERO_RISK] = wc.zero_risk;
+  v[RT_ST_SHADOW_NODE_VISITS] = shade ? wc.nodes : 0u, v[RT_ST_SHADOW_TRI_TESTS] = shade ? wc.tris : 0u;
+  v[RT_ST_SHADOW_UNPROVEN] = wc.sh_unproven, v[RT_ST_CLOSEST_UNPROVEN] = wc.cl_unproven;
 #pragma unroll
   for (int k = 0; k < RT_NSTATS; k++)
     if (lane == 0 && v[k])
@@ -180,7 +185,7 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     const uint64_t hm = __ballot(hit);
     if (hm == 0) break;
     uint32_t base = 0;
-    if (w.lane == 0) base = atomicAdd(p.hit_count + 32u * x, (uint32_t)__popcll(hm));
+    if (w.lane == 0) base = atomicAdd(p.hit_count + RT_HIT_STRIDE * x, (uint32_t)__popcll(hm));
     base = uni(base);
     bool deep = false;
     if (hit) {
@@ -412,7 +417,7 @@ __global__ __launch_bounds__(64, ACCEL == RT_ACCEL_FLAT_D ? RT_FLAT_SHADE_MIN_WA
   bool first_chunk = true;
   for (;;) {
     const uint32_t x = (home + probe) & 7u;
-    const uint32_t hc = p.hit_count[32u * x];
+    const uint32_t hc = p.hit_count[RT_HIT_STRIDE * x];
     const uint32_t n = hc < p.hit_cap ? hc : p.hit_cap;
     const uint32_t stride = p.shade_stride > 1u ? p.shade_stride : 1u;  // verification only
     const uint32_t first = p.shade_first;
@@ -423,7 +428,7 @@ __global__ __launch_bounds__(64, ACCEL == RT_ACCEL_FLAT_D ? RT_FLAT_SHADE_MIN_WA
       q = (uint32_t)blockIdx.x >> 3;
       first_chunk = false;
     } else {
-      if (lane == 0) q = atomicAdd(p.shade_counter + 32u * x, 1u);
+      if (lane == 0) q = atomicAdd(p.shade_counter + RT_HIT_STRIDE * x, 1u);
       q = uni(q) + (gridDim.x - x + 7u) / 8u;
     }
     if (q >= (ns + 63u) / 64u) {
@@ -494,7 +499,7 @@ __global__ __launch_bounds__(256) void oob_fix_kernel(KParams p, uint32_t nprim)
       if (h) mine |= 1u << li;
     }
     if (mine) atomicOr(&bits, mine);
-    if (risk) atomicAdd(p.stats + 18, 1ull);  // shadow_zero_risk
+    if (risk) atomicAdd(p.stats + RT_ST_SHADOW_ZERO_RISK, 1ull);
     __syncthreads();
     if (threadIdx.x == 0 && bits) atomicOr(&p.oob[e].w, bits);
     __syncthreads();
@@ -545,7 +550,7 @@ __global__ __launch_bounds__(256) void oob_fix_batch_kernel(KParams p, uint32_t 
       if (any_hit_rec(q.r, a0, a1, a2, risk)) atomicOr(&p.oob[q.e].w, 1u << q.li);
     }
   }
-  if (risk) atomicAdd(p.stats + 18, 1ull);  // shadow_zero_risk
+  if (risk) atomicAdd(p.stats + RT_ST_SHADOW_ZERO_RISK, 1ull);
 }
 
 // ... then each entry's record shaded again with the decided lights
@@ -584,18 +589,23 @@ __global__ __launch_bounds__(256) void fold_kernel(KParams p) {
   if (idx == 0 && p.frame_check) {  // every earlier launch of the frame has ended (same stream)
     uint32_t f = 0;
     for (int x = 0; x < RT_HIT_REGIONS; x++)
-      if (p.hit_count[32 * x] > p.hit_cap) f |= RT_FRAME_HITBUF;
+      if (p.hit_count[RT_HIT_STRIDE * x] > p.hit_cap) f |= RT_FRAME_HITBUF;
     unsigned long long s[RT_NSTATS] = {};
     for (int set = 0; set < RT_STAT_SETS; set++)
       for (int k = 0; k < RT_NSTATS; k++) s[k] += p.stats[set * RT_STAT_STRIDE + k];
-    if (s[5]) f |= RT_FRAME_DEPTH;
-    if (s[6] || s[18]) f |= RT_FRAME_ZERO;
-    if (s[21] || s[22] || (p.oob_count && *p.oob_count > p.oob_cap)) f |= RT_FRAME_UNPROVEN;
+    auto raised = [&s](uint32_t flag) {  // a slot that raises `flag` is not zero
+      bool any = false;
+      for (uint32_t k = 0; k < RT_NSTATS; k++) any = any || (rt_stat_frame_flag(k) == flag && s[k]);
+      return any;
+    };
+    if (raised(RT_FRAME_DEPTH)) f |= RT_FRAME_DEPTH;
+    if (raised(RT_FRAME_ZERO)) f |= RT_FRAME_ZERO;
+    if (raised(RT_FRAME_UNPROVEN) || (p.oob_count && *p.oob_count > p.oob_cap)) f |= RT_FRAME_UNPROVEN;
     if (p.list_flag && *p.list_flag) f |= RT_FRAME_LISTS;
     atomicOr(p.frame_check, (unsigned long long)f);
     atomicAdd(p.frame_check + 1, 1ull);
-    atomicAdd(p.frame_check + 2, s[0]);
-    atomicAdd(p.frame_check + 3, s[1]);
+    atomicAdd(p.frame_check + 2, s[RT_ST_CLOSEST]);
+    atomicAdd(p.frame_check + 3, s[RT_ST_SHADOW]);
   }
   if (idx >= (uint32_t)p.ntiles_local * 64u) return;
   const uint32_t t = idx >> 6, lane = idx & 63u;

@@ -217,11 +217,11 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
   DevBuf<float4> term;
   DevBuf<unsigned long long> st;
   int rc = RT_OK;
-  uint32_t hc[RT_HIT_REGIONS * 32];
+  uint32_t hc[RT_HIT_REGIONS * RT_HIT_STRIDE];
   unsigned long long nsh = 0;
   for (uint32_t li = 0; li < c->nlight; li++) nsh += c->light_type[li] == 1 || c->light_type[li] == 2;
   if (lit[0].alloc(n) != hipSuccess || lit[1].alloc(n) != hipSuccess || term.alloc(n) != hipSuccess ||
-      ctr.alloc(RT_HIT_REGIONS * 32) != hipSuccess || st.alloc(kStatBytes / sizeof(unsigned long long)) != hipSuccess)
+      ctr.alloc(RT_HIT_REGIONS * RT_HIT_STRIDE) != hipSuccess || st.alloc(kStatBytes / sizeof(unsigned long long)) != hipSuccess)
     return rt_set_error(RT_EHIP, "hipMalloc shadow verification buffers");
   for (int pass = 0; pass < 2 && !rc; pass++) {
     KParams p = c->last_p;
@@ -242,7 +242,7 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
     }
     if (pass == 1) p.oob = nullptr;
     if (hipMemsetAsync(lit[pass], 0xff, n * sizeof(uint32_t), s) != hipSuccess ||
-        hipMemsetAsync(ctr, 0, RT_HIT_REGIONS * 32 * sizeof(uint32_t), s) != hipSuccess ||
+        hipMemsetAsync(ctr, 0, RT_HIT_REGIONS * RT_HIT_STRIDE * sizeof(uint32_t), s) != hipSuccess ||
         (p.oob && hipMemsetAsync(p.oob_count, 0, sizeof(uint32_t), s) != hipSuccess) ||
         rt_launch_shade(&p, dacc, 0, dacc == RT_ACCEL_FLAT_D ? 0 : c->policy, g, s) != hipSuccess ||
         rt_launch_shade_fixup(&p, c->nprim, s) != hipSuccess ||
@@ -258,7 +258,7 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
     return rt_set_error(RT_EHIP, "shadow verification read-back");
   std::memset(out, 0, 4 * sizeof *out);
   for (int x = 0; x < RT_HIT_REGIONS; x++) {
-    const size_t cnt = hc[32 * x] < hit_cap ? hc[32 * x] : hit_cap;
+    const size_t cnt = hc[RT_HIT_STRIDE * x] < hit_cap ? hc[RT_HIT_STRIDE * x] : hit_cap;
     for (size_t k = first; k < cnt; k += (stride ? stride : 1)) {
       const size_t a = (size_t)x * hit_cap + k;
       out[0]++;

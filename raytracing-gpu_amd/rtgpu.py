@@ -674,9 +674,10 @@ class Context:
         self._check_render(lib().rt_hip_stats(self.h, C.byref(st)), "rt_hip_stats")
         return st.as_dict()
 
-    # rt_hip_frame_check flag bits (csrc/rt_kernels.h RT_FRAME_*)
+    # rt_hip_frame_check flag bits (csrc/rt_counters.h RT_FRAME_*)
     FRAME_FLAGS = {1: "hit records past the buffer (RT_EHITBUF)", 2: "bounce limit / stack overflow (RT_EDEPTH)",
-                   4: "zero interpolated normal (RT_EZERONORMAL)", 8: "undecided exact shadow queries (RT_EINEXACT)",
+                   4: "zero interpolated normal (RT_EZERONORMAL)",
+                   8: "unproven or undecided exact shadow / reflection queries (RT_EINEXACT)",
                    16: "asynchronous list build overflow (RT_EHITBUF)"}
 
     def frame_check(self):

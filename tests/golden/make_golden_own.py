@@ -87,9 +87,11 @@ def main():
                           "closest": int(m.group(1)), "shadow": int(m.group(2)),
                           "f32_sha256": hashlib.sha256(data).hexdigest(), "ppm_md5": ppm_md5})
             print(cases[-1])
+    with open(os.path.join(OUT, "manifest.json")) as f:  # recordings made elsewhere stay listed
+        fixtures = json.load(f).get("fixtures", [])
     with open(os.path.join(OUT, "manifest.json"), "w") as f:
         json.dump({"generator": "tests/golden/make_golden_own.py (reference cpu/rt via oracle/_ref/rt_probe)",
-                   "cases": cases}, f, indent=1)
+                   "cases": cases, "fixtures": fixtures}, f, indent=1)
 
 
 if __name__ == "__main__":
