@@ -77,7 +77,7 @@ int rt_hip_frame_kernel_times(rt_hip_ctx *ctx, int n, float *trace_ms, float *sh
                               float *fold_ms);
 /* Instrumented build: also count node visits and triangle tests (slower). */
 int rt_hip_set_count_work(rt_hip_ctx *ctx, int enable);
-/* Shader clocks of every work item -- (tile t, sample s) at index 4t + s,
+/* Shader clocks of every work item -- (tile t, 4x4-pixel quarter q, all four samples) at index 4t + q,
  * rank-local tile order -- of the last instrumented render (n <= 4 x tiles
  * of the rank): the load-balance picture of a frame. */
 int rt_hip_tile_cycles(rt_hip_ctx *ctx, unsigned long long *out, size_t n);

@@ -114,7 +114,7 @@ struct rt_hip_ctx {
     return std::min({d_hit.cap() / 2, d_hit_prev.cap(), d_hit_term.cap()}) / RT_HIT_REGIONS;
   }
   size_t hit_need = 0;              // per region: what the last overflowing frame needed
-  DevBuf<uint32_t> d_last;          // per (item, lane): a path's deepest record
+  DevBuf<uint32_t> d_last;          // per (item, lane), item = (tile, quarter): a path's deepest record
   // G-buffer (rt_hip_set_gbuffer): the capturing trace's record per (item,
   // lane), and the frame whose render filled it (gb_valid: rt_hip_gbuffer may
   // read it; rank / nranks / stream are last_p's and last_stream)
@@ -227,7 +227,7 @@ struct rt_hip_ctx {
   // grid: the same frame's next work order puts its long items first
   ListShape cost_hist;
   uint32_t cost_waves = 0;
-  DevBuf<uint32_t> d_item_cost;  // 4 x ntiles_local
+  DevBuf<uint32_t> d_item_cost;  // 4 x ntiles_local: one per (tile, quarter)
   int last_async = 0;                 // the last render's lists came from an asynchronous build
   unsigned long long cand_prims = 0, cand_entries = 0, cand_global = 0;
   // triangle-parallel lists (rt_hip_cand_produce / rt_hip_cand_consume)

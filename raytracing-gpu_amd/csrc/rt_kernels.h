@@ -124,7 +124,7 @@ struct KParams {
   float4* hit_term;             // per record: color_mul(apply_light(...), coef), rgb
   uint32_t* hit_count;          // RT_HIT_REGIONS append counters, RT_HIT_STRIDE words apart
   uint32_t hit_cap;             // records per region
-  uint32_t* last;               // per (item, lane): the path's deepest record (RT_NO_REC)
+  uint32_t* last;               // per (item, lane), rt_tiles.h rt_item_slot: the path's deepest record (RT_NO_REC)
   uint32_t* shade_counter;      // RT_HIT_REGIONS chunk counters of shade_kernel, RT_HIT_STRIDE apart
   // shadow verification (rt_hip_verify_shadows; NULL / 0 in renders): the
   // shade pass writes each shaded record's unshadowed-light mask (lights
@@ -158,7 +158,7 @@ struct KParams {
   float scene_r;                // scene box half-extent (max-norm)
   float eps_rel;                // culling slack, rt_cull.h rt_cull_eps()
   float eps_rel_cam;            // the same for camera rays (bounce depth 0)
-  unsigned long long* tile_cycles;  // COUNT pass: shader clocks of each work item (tile, sample) (NULL: none)
+  unsigned long long* tile_cycles;  // COUNT pass: shader clocks of each work item (tile, quarter) (NULL: none)
   // camera-ray candidate lists (csrc/rt_cand.hip); cand_start == NULL: none
   const uint32_t* cand_start;   // ntiles_local + 1 offsets into cand
   const uint32_t* cand;         // prims
@@ -168,7 +168,7 @@ struct KParams {
   const float4* tri_prim;       // prim-order triangle records
   const float* cand_skip;       // per cand entry: lower bound of new_dist - |pos - o| (depth skip)
   const uint32_t* tile_order;   // trace_kernel's work order: position -> rank-local tile (NULL: identity)
-  // the trace's per-item cost (shader clocks of each (tile, sample) item,
+  // the trace's per-item cost (shader clocks of each (tile, quarter) item,
   // saturated to 32 bits) and their sum (zeroed before launch), for the next
   // frame's work order (rt_cand_order); NULL: not recorded
   uint32_t* item_cost;

@@ -44,16 +44,16 @@
 
 namespace rt {
 
-// PPM (row, col) of lane `lane` of rank-local tile t (rt_hip.h "Image
-// tiling", csrc/rt_tiles.h): 8 x 8 pixels, lane = row * 8 + col.
-__device__ __forceinline__ void tile_pixel(const KParams& p, uint32_t t, int lane, int& pr,
+// PPM (row, col) of pixel (row, col) of rank-local tile t (rt_hip.h "Image
+// tiling", csrc/rt_tiles.h): 8 x 8 pixels.
+__device__ __forceinline__ void tile_pixel(const KParams& p, uint32_t t, int row, int col, int& pr,
                                            int& pc) {
   int tx, ty;
   const int tb = rt_block_side(p.nranks);
   rt_tile_xy(t, (uint32_t)p.rank, (uint32_t)p.nranks, (uint32_t)rt_blocks_x(p.tiles_x, tb), (uint32_t)tb,
              &tx, &ty);
-  pr = ty * 8 + (lane >> 3);
-  pc = tx * 8 + (lane & 7);
+  pr = ty * 8 + row;
+  pc = tx * 8 + col;
 }
 
 // The wave's counters are wave totals already: one atomic per counter per
@@ -101,13 +101,20 @@ __device__ __forceinline__ size_t rec_addr(const KParams& p, uint32_t idx) {
   return (size_t)(idx & 7u) * p.hit_cap + (idx >> 3);
 }
 
-// Camera sample smp of lane `lane` of rank-local tile t: its ray (origin on
-// the film, direction towards the eye) exactly as cpu/raytracer.c:55-60
-// computes it; false when the lane's pixel lies outside the framebuffer's
-// even-sized area (its ray is still defined).
-__device__ __forceinline__ bool camera_sample(const KParams& p, uint32_t t, int smp, int lane, f3& point, f3& dir) {
-  int pr, pc;
-  tile_pixel(p, t, lane, pr, pc);
+// The camera sample of lane `lane` of item q of rank-local tile t (its pixel
+// and sample smp by rt_item_pixel): its ray (origin on the film, direction
+// towards the eye) exactly as cpu/raytracer.c:55-60 computes it; false when
+// the lane's pixel lies outside the framebuffer's even-sized area (its ray is
+// still defined).
+__device__ __forceinline__ bool camera_sample(const KParams& p, uint32_t t, uint32_t q, int lane, int& smp,
+                                              f3& point, f3& dir) {
+  int row, col, pr, pc;
+  // (the lane's share of the map does not change from item to item: opaque,
+  // or it is hoisted out of trace_kernel's item loop and holds registers
+  // across every walk -- 8 B more scratch per lane)
+  asm volatile("" : "+v"(lane));
+  rt_item_pixel(q, (uint32_t)lane, &row, &col, &smp);
+  tile_pixel(p, t, row, col, pr, pc);
   // PPM (row, col) -> framebuffer slot (j, i) of cpu/raytracer.c:71,128-134
   const int ii = p.W - pc, jj = p.H - pr;
   const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 && jj <= 2 * (p.H / 2);
@@ -237,13 +244,17 @@ __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void trace_kernel(KParams p
   w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
   w.stage = s_stage;
   w.lane = lane;
-  // Work item = (tile t, sample s): the four samples of a tile run on four
+  // Work item = (tile t, quarter q): a tile's 256 camera rays run on four
   // waves, so a tile of long mirror paths (C2: the worst tile cost 7.7x a
-  // balanced schedule's whole frame, tools/tile_cost.py) is no longer one
-  // wave's serial critical path.  Items come in 8 streams, stream x = the
+  // balanced schedule's whole frame, tools/tile_cost.py) is not one wave's
+  // serial critical path.  A wave takes the four samples of a 4x4-pixel
+  // quarter (rt_item_pixel, csrc/rt_tiles.h), not one sample of the 8x8
+  // tile: the packet walk is wave-serial over the union of its lanes'
+  // walks, and a quarter's cone crosses fewer leaves that most of its rays
+  // never enter.  Items come in 8 streams, stream x = the
   // tiles t = x (mod 8) in scanline order, 4 items each: workgroup b (on XCD
   // b mod 8, the dispatcher's round robin) pulls from stream b mod 8, so a
-  // tile's samples share one XCD's L2, all XCDs work on the same few tile
+  // tile's quarters share one XCD's L2, all XCDs work on the same few tile
   // rows (their geometry stays in the Infinity Cache), and the item counters'
   // atomic traffic is split 8 ways; a drained stream's waves move on to the
   // next.  Each item writes its lanes' deepest hit records.  With camera
@@ -278,17 +289,17 @@ __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void trace_kernel(KParams p
       continue;
     }
     const uint32_t pos = 8u * (q >> 2) + x;  // the tile's place in the work order
-    const uint32_t u = 4u * (p.tile_order ? p.tile_order[pos] : pos) + (q & 3u);  // item 4t + s
+    const uint32_t u = 4u * (p.tile_order ? p.tile_order[pos] : pos) + (q & 3u);  // item 4t + quarter
     const bool prio = pos < n_heavy;
     if (prio) __builtin_amdgcn_s_setprio(3);
     const unsigned long long c0 = (COUNT || p.item_cost) ? __builtin_readcyclecounter() : 0ull;
     const uint32_t ph0[3] = {wc.cy_cam, wc.cy_cand, wc.cy_sec};
     wc.sec_lane_nodes = wc.sec_lane_tris = 0;
     const uint32_t t = u >> 2;
-    const int smp = (int)(u & 3u);
+    int smp;
     f3 point, dir;
-    const bool valid = camera_sample(p, t, smp, lane, point, dir);
-    if (smp == 0) wc.pixels += (uint32_t)__popcll(__ballot(valid));
+    const bool valid = camera_sample(p, t, u & 3u, lane, smp, point, dir);
+    wc.pixels += (uint32_t)__popcll(__ballot(valid && smp == 0));
     Capture cap;
     p.last[(size_t)u * 64 + lane] =
         trace_path<ACCEL, COUNT, POL>(p, valid, point, dir, x, stk, w, wc, t, cap, 0, 1.0f, RT_NO_REC);
@@ -578,12 +589,18 @@ __global__ __launch_bounds__(64) void oob_reshade_kernel(KParams p) {
 
 namespace rt {
 
-// A pixel's four samples (trace_kernel items 4t..4t+3): each sample's path
+// A pixel's four samples (four neighbouring lanes of one trace_kernel item,
+// their deepest records one 16-byte load: rt_pixel_slots): each sample's path
 // terms summed deepest-first, acc = color_add(reflected, term)
 // (cpu/raytracer.c:29-30), then acc = color_add(acc, color_mul(s, 0.25)) over
 // the samples (i,j), (i,j+.5), (i+.5,j), (i+.5,j+.5) (cpu/raytracer.c:55-68);
 // pixels outside the framebuffer's even-sized area are 0.  One thread per
-// pixel of the rank's tile buffer.
+// pixel of the rank's tile buffer (slot = row * 8 + col).  (Neighbouring
+// hit records are now a pixel's samples, so neighbouring threads' chain
+// loads are four records apart: fold 0.127 -> 0.143 ms on C5, 0.061 -> 0.097
+// on C3, beside shade's 1.84 -> 1.69 from the same order.  One thread per
+// (item, lane) with the samples brought together by __shfl read them side by
+// side but ran four times the threads: 0.245 and 0.076 ms)
 __global__ __launch_bounds__(256) void fold_kernel(KParams p) {
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx == 0 && p.frame_check) {  // every earlier launch of the frame has ended (same stream)
@@ -610,14 +627,18 @@ __global__ __launch_bounds__(256) void fold_kernel(KParams p) {
   if (idx >= (uint32_t)p.ntiles_local * 64u) return;
   const uint32_t t = idx >> 6, lane = idx & 63u;
   int pr, pc;
-  tile_pixel(p, t, (int)lane, pr, pc);
+  const int row = (int)(lane >> 3), col_ = (int)(lane & 7u);
+  tile_pixel(p, t, row, col_, pr, pc);
   const int ii = p.W - pc, jj = p.H - pr;
   const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 &&
                      jj <= 2 * (p.H / 2);
+  const uint4 l4 = *(const uint4*)(p.last + rt_pixel_slots(t, row, col_));
+  const uint32_t last[4] = {l4.x, l4.y, l4.z, l4.w};
   col acc = init_color(0.0f, 0.0f, 0.0f);
+#pragma unroll
   for (int smp = 0; smp < 4; smp++) {
     col sc = init_color(0.0f, 0.0f, 0.0f);
-    uint32_t r = p.last[((size_t)t * 4 + (size_t)smp) * 64 + lane];
+    uint32_t r = last[smp];
     while (r != RT_NO_REC && (r >> 3) < p.hit_cap) {
       const size_t a = rec_addr(p, r);
       const float4 tm = p.hit_term[a];
@@ -693,14 +714,15 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
   const uint32_t slot = (uint32_t)(g >> 2), smp = (uint32_t)g & 3u;
   const uint32_t t = slot >> 6, lane = slot & 63u;
   int pr, pc;
-  tile_pixel(p, t, (int)lane, pr, pc);
+  const int row = (int)(lane >> 3), col_ = (int)(lane & 7u);
+  tile_pixel(p, t, row, col_, pr, pc);
   const int ii = p.W - pc, jj = p.H - pr;
   const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 &&
                      jj <= 2 * (p.H / 2);
   uint32_t prim = 0xffffffffu, obj = 0xffffffffu, queries = 0, dist = 0x7f800000u;
   float4 h0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), h1 = h0;
   if (valid) {
-    const uint4 c = p.capture[((size_t)t * 4 + smp) * 64 + lane];
+    const uint4 c = p.capture[rt_item_slot(t, row, col_, (int)smp)];
     queries = c.w;
     if (c.x != 0xffffffffu) {
       prim = c.x;

@@ -28,6 +28,7 @@
 // (cpu/raytracer.c:92-127); this is the same idea sized for 8 GPUs x 256 CUs.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -96,6 +97,40 @@ RT_TILES_FN void rt_tile_xy(uint32_t t, uint32_t r, uint32_t n, uint32_t blocks_
   const uint32_t by = lo, bx = rt_row_res(by, n, r) + (j - rt_rank_rows_blocks(by, blocks_x, n, r)) * n;
   *tx = (int)(bx * tb + k % tb);
   *ty = (int)(by * tb + k / tb);
+}
+
+// ---- trace work items: which rays of a tile one wave takes
+// A tile's 256 camera rays (64 pixels x the 4 supersamples of
+// cpu/raytracer.c:55-58, sample smp = 2 * (k step) + (l step)) are traced as 4
+// work items of 64 lanes, item 4t + q of rank-local tile t.  Item q is the
+// tile's 4x4-pixel quarter q = 2 * (row >= 4) + (col >= 4) with all four
+// samples of its 16 pixels: lane = 4 * (4 * (row & 3) + (col & 3)) + smp.
+// The rays of a wave then span a quarter of the tile's cone, so the packet
+// walk's union of nodes and leaves is close to what each ray needs (DESIGN.md
+// §4), and a pixel's four slots of the per-(item, lane) arrays
+// (KParams::last, KParams::capture) are contiguous in sample order:
+// rt_pixel_slots.  This header is the only place that spells the layout out.
+#define RT_TILE_ITEMS 4  // work items per tile
+
+// lane `lane` of a tile's item q: its pixel (row, col) in the 8x8 tile, its sample
+RT_TILES_FN void rt_item_pixel(uint32_t q, uint32_t lane, int* row, int* col, int* smp) {
+  const uint32_t px = lane >> 2;  // pixel of the quarter, row-major
+  *row = (int)(((q >> 1) << 2) | (px >> 2));
+  *col = (int)(((q & 1u) << 2) | (px & 3u));
+  *smp = (int)(lane & 3u);
+}
+
+// index of tile t's pixel (row, col), sample 0, in the per-(item, lane)
+// arrays; samples 1..3 follow it (the index is a multiple of 4)
+RT_TILES_FN size_t rt_pixel_slots(uint32_t t, int row, int col) {
+  const uint32_t q = 2u * (uint32_t)(row >= 4) + (uint32_t)(col >= 4);
+  const uint32_t lane = 4u * (4u * ((uint32_t)row & 3u) + ((uint32_t)col & 3u));
+  return ((size_t)t * RT_TILE_ITEMS + q) * 64 + lane;
+}
+
+// the inverse of rt_item_pixel: index of (tile t, pixel (row, col), sample smp)
+RT_TILES_FN size_t rt_item_slot(uint32_t t, int row, int col, int smp) {
+  return rt_pixel_slots(t, row, col) + (size_t)smp;
 }
 
 // rank and rank-local index of tile (tx, ty)

@@ -46,7 +46,7 @@ def run(scene, W, H, tag):
            "kernels_ms": [list(k) for k in kt],
            "max_item": float(items.max()), "mean_item": float(items.mean()),
            "worst_items": [{"row": int(tys[i // 4]) * 8, "col": int(txs[i // 4]) * 8,
-                            "sample": int(i % 4), "clocks": float(items[i])} for i in order]}
+                            "quarter": int(i % 4), "clocks": float(items[i])} for i in order]}
     ctx.close()
     print(json.dumps(res, default=float), flush=True)
     return res

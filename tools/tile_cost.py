@@ -59,7 +59,7 @@ def main():
                 raise
     nt = rtgpu.rank_tile_count(a.W, a.H, a.rank, a.nranks)  # rank-local tiles (csrc/rt_tiles.h order)
     txs, tys = rtgpu.tile_xy(np.arange(nt), a.rank, a.nranks, a.W, a.H)
-    items = ctx.tile_cycles(4 * nt).astype(np.float64)  # item 4t + s = (tile t, sample s)
+    items = ctx.tile_cycles(4 * nt).astype(np.float64)  # item 4t + q = (tile t, quarter q)
     c = items.reshape(-1, 4).sum(axis=1)
     # trace kernel phases (shadow queries run in the shade kernel, not per item)
     ph = {name: ctx.tile_phase_cycles(k, 4 * nt).astype(np.float64)
@@ -78,7 +78,7 @@ def main():
         "max_over_mean": c.max() / c.mean(),
         "top1pct_share": float(c[order[: max(1, len(c) // 100)]].sum() / tot),
         # a persistent schedule of 4096 waves cannot finish before its most
-        # expensive work item (one sample of a tile), nor before total / 4096
+        # expensive work item (one 4x4-pixel quarter of a tile), nor before total / 4096
         "max_item": items.max(),
         "bound_tail_over_balanced": items.max() / (tot / 4096.0),
         # items per wave of the persistent grid (5 waves x 1024 SIMDs), and the
