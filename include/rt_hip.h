@@ -364,7 +364,7 @@ int rt_hip_render_image_gbuffer(rt_hip_ctx *ctx, const rt_frame *frame, float *h
  * 255) in gpu/rt's PNG row order.  stats as rt_hip_stats (camera = pixels =
  * high-resolution rays).  Camera rays keep the exactness of cpu mode: the
  * per-frame candidate lists of the 3x frame's one-ray-per-pixel camera
- * (csrc/rt_cand.hip, CandParams::compat). */
+ * (csrc/rt_cand.h CandParams::compat, csrc/rt_cand_geom.h pixel_range). */
 int rt_hip_render_compat(rt_hip_ctx *ctx, const rt_camera *cam, unsigned char *h_rgba,
                          rt_stats *stats);
 /* Drop-in for gpu/rt's main (gpu/rt.cpp:56-97): load, render in

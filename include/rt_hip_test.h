@@ -137,7 +137,7 @@ int rt_hip_set_camera_bound_scale(rt_hip_ctx *ctx, double scale);
  * triangle whose footprint spans more than 2 tile rows or 32 tiles are kept
  * only where the error bound evaluated for that tile's own rays (their
  * directions, origins and grazing cosine) still reaches the tile
- * (csrc/rt_cand.hip tile_keep) -- proven like the per-triangle bound, so the
+ * (csrc/rt_cand_geom.h tile_keep) -- proven like the per-triangle bound, so the
  * lists stay exact.  0: the per-triangle footprints alone (A/B timing). */
 int rt_hip_set_camera_refine(rt_hip_ctx *ctx, int enable);
 /* Host-only survey of the camera candidate lists of a scene's frame (no

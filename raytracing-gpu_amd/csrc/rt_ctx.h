@@ -3,7 +3,8 @@
 //   rt_hip.cpp     context lifetime, settings, light buffers, render, stats,
 //                  assemble, the gpu/rt compatibility mode, rt_raytrace
 //   rt_lists.cpp   the camera rays' candidate lists (per rank and
-//                  triangle-parallel produce / consume) and their surveys
+//                  triangle-parallel produce / consume) and the entry points
+//                  of their host mirrors (rt_cand_host.cpp, which needs no context)
 //   rt_verify.cpp  probes, verification, timing and measurement hooks
 //   rt_multi.cpp   rt_raytrace_multi: N GPUs, RCCL exchange and gather
 // Internal, not part of the ABI.
@@ -172,7 +173,7 @@ struct rt_hip_ctx {
   // light buffers, the per-node multiplier walk where a light has none
   int exact_shadows = 1;
   size_t tile_cycles_n = 0;         // items of the last work-counting pass (d_tile_cycles: 6 per item)
-  // exact camera rays (csrc/rt_cand.hip)
+  // exact camera rays (csrc/rt_cand.hip; launchers in csrc/rt_cand.h)
   int exact_camera = 1;
   // the big footprints' entries refined per tile (rt_hip_set_camera_refine,
   // default on; RT_CAND_REFINE=0 at context creation turns it off)
@@ -264,10 +265,6 @@ static inline void lists_changed(rt_hip_ctx* c) {
   c->pknown.valid = 0;
 }
 
-// The unit of the culling slacks: eps_ulps of them, relative to the
-// origin-to-geometry distance (2^-24; DESIGN.md "Conservative culling").
-static constexpr float kSlackUnit = 5.9604645e-8f;
-
 // Kernel parameters with the context's scene filled in and everything else
 // zero: what every launch that takes a KParams starts from (the renders, the
 // probes of rt_verify.cpp).
@@ -294,19 +291,17 @@ static inline KParams scene_params(const rt_hip_ctx* c) {
   return p;
 }
 
-int cand_params(const rt_frame* f, const float scene_c[3], float scene_r, float eps_ulps, double bound_scale,
-                int rank, int nranks, CandParams* out, int compat = 0);
-
-static inline int tiles_x_of(int W) { return (W + 7) / 8; }
-static inline int tiles_y_of(int H) { return (H + 7) / 8; }
-
-// tiles rank `rank` renders (whole blocks, edge padding included; csrc/rt_tiles.h)
-static inline int rank_tile_count(int W, int H, int rank, int nranks) {
-  const int tb = rt_block_side(nranks);
-  return (int)(rt_rank_blocks((uint32_t)rt_blocks_x(tiles_x_of(W), tb), (uint32_t)rt_blocks_y(tiles_y_of(H), tb),
-                              (uint32_t)nranks, (uint32_t)rank) * tb * tb);
+// Centre and half extent (max-norm) of the scene's bounding box, in float:
+// what the culling slack is relative to (rt_hip_create keeps them in the
+// context; the host surveys derive the same values).  Zeros for an empty scene.
+static inline void scene_extent(const rt_flat_scene& fs, float c[3], float* r) {
+  *r = 0;
+  for (int a = 0; a < 3; a++) {
+    float lo = fs.ntri ? fs.scene_lo[a] : 0.0f, hi = fs.ntri ? fs.scene_hi[a] : 0.0f;
+    c[a] = 0.5f * (lo + hi);
+    *r = std::fmax(*r, 0.5f * (hi - lo));
+  }
 }
-
 
 // shared between the files above (defined in the file named)
 int shadow_prepare(rt_hip_ctx* c, hipStream_t s);                                  // rt_hip.cpp

@@ -367,12 +367,10 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
       }
     }
   }
+  scene_extent(fs, c->scene_c, &c->scene_r);
   for (int a = 0; a < 3; a++) {
-    float lo = fs.ntri ? fs.scene_lo[a] : 0.0f, hi = fs.ntri ? fs.scene_hi[a] : 0.0f;
-    c->scene_lo[a] = lo;
-    c->scene_hi[a] = hi;
-    c->scene_c[a] = 0.5f * (lo + hi);
-    c->scene_r = std::fmax(c->scene_r, 0.5f * (hi - lo));
+    c->scene_lo[a] = fs.ntri ? fs.scene_lo[a] : 0.0f;
+    c->scene_hi[a] = fs.ntri ? fs.scene_hi[a] : 0.0f;
   }
   c->info.triangles = fs.ntri;
   c->info.tri_refs = fs.nrec;
@@ -590,7 +588,7 @@ static int render_refuse(const rt_hip_ctx* c, const rt_frame* f, int rank, int n
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   // cpu/rt's frame is even-sized (rt_frame_from_camera; its output for odd
   // sizes is undefined, cpu/raytracer.c:89-91,128-134); the camera sample
-  // model of the candidate lists assumes it (rt_cand.hip pixel_range)
+  // model of the candidate lists assumes it (rt_cand_geom.h pixel_range)
   if ((f->width | f->height) & 1)
     return rt_set_error(RT_EINVAL, "frame %dx%d: cpu/rt renders even sizes only", f->width, f->height);
   // the G-buffer's capture exists for the default kernels only (its own
@@ -1352,7 +1350,7 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
     p.sh_omax = c->sh_omax;
   }
   // exact camera rays in this mode too: the candidate lists of the 3x frame's
-  // one-sample-per-pixel camera (csrc/rt_cand.hip CandParams::compat)
+  // one-sample-per-pixel camera (csrc/rt_cand.h CandParams::compat)
   c->cand_prims = c->cand_entries = c->cand_global = 0;
   c->d_cand_valid = nullptr;
   if (c->accel == RT_ACCEL_OCTREE && c->d_node && c->exact_camera) {

@@ -159,7 +159,7 @@ struct KParams {
   float eps_rel;                // culling slack, rt_cull.h rt_cull_eps()
   float eps_rel_cam;            // the same for camera rays (bounce depth 0)
   unsigned long long* tile_cycles;  // COUNT pass: shader clocks of each work item (tile, quarter) (NULL: none)
-  // camera-ray candidate lists (csrc/rt_cand.hip); cand_start == NULL: none
+  // camera-ray candidate lists (built by csrc/rt_cand.hip, ordered by rt_cand_entries.h); cand_start == NULL: none
   const uint32_t* cand_start;   // ntiles_local + 1 offsets into cand
   const uint32_t* cand;         // prims
   const uint32_t* cand_global;  // prims every camera ray tests

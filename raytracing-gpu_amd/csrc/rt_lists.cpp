@@ -1,9 +1,11 @@
-// rt_lists.cpp -- the camera rays' candidate lists on the host side
-// (DESIGN.md §2 "Exact camera rays", §4 "Candidate-list kernels"): frame
-// constants, the per-rank build (cand_prepare: fast path -> classification ->
-// emission -> refinement -> compaction -> sort -> offsets -> work order), the
-// triangle-parallel produce / consume of an N-rank frame, the host
-// re-derivation that verifies them, and the host surveys.
+// rt_lists.cpp -- the camera rays' candidate lists on the context's side
+// (DESIGN.md §2 "Exact camera rays", §4 "Candidate-list kernels"): the
+// per-rank build (cand_prepare: fast path -> classification -> emission ->
+// refinement -> compaction -> sort -> offsets -> work order), the
+// triangle-parallel produce / consume of an N-rank frame, and the entry
+// points that hand a scene or the last frame's device-built lists to the host
+// mirrors.  The frame constants (cand_params) and the mirrors themselves need
+// no context and live in rt_cand_host.cpp.
 #include "rt_ctx.h"
 
 extern "C" int rt_cand_refine_sample(const rt_scene* scene, float eps_ulps, double bound_scale, unsigned stride,
@@ -20,12 +22,8 @@ extern "C" int rt_cand_refine_sample(const rt_scene* scene, float eps_ulps, doub
   rt_flat_scene fs;
   rc = rt_flatten(scene, RT_ACCEL_FLAT, &fs);
   if (rc) return rc;
-  float sc[3], sr = 0;
-  for (int a = 0; a < 3; a++) {  // as rt_hip_create
-    float lo = fs.ntri ? fs.scene_lo[a] : 0.0f, hi = fs.ntri ? fs.scene_hi[a] : 0.0f;
-    sc[a] = 0.5f * (lo + hi);
-    sr = std::fmax(sr, 0.5f * (hi - lo));
-  }
+  float sc[3], sr;
+  scene_extent(fs, sc, &sr);  // as rt_hip_create
   CandParams cp;
   rc = cand_params(&f, sc, sr, eps_ulps, bound_scale, 0, 1, &cp, compat ? 1 : 0);
   if (!rc) {
@@ -45,12 +43,8 @@ extern "C" int rt_cand_survey(const rt_scene* scene, float eps_ulps, double boun
   rt_flat_scene fs;
   rc = rt_flatten(scene, RT_ACCEL_FLAT, &fs);
   if (rc) return rc;
-  float sc[3], sr = 0;
-  for (int a = 0; a < 3; a++) {  // as rt_hip_create
-    float lo = fs.ntri ? fs.scene_lo[a] : 0.0f, hi = fs.ntri ? fs.scene_hi[a] : 0.0f;
-    sc[a] = 0.5f * (lo + hi);
-    sr = std::fmax(sr, 0.5f * (hi - lo));
-  }
+  float sc[3], sr;
+  scene_extent(fs, sc, &sr);  // as rt_hip_create
   CandParams cp;
   rc = cand_params(&f, sc, sr, eps_ulps, bound_scale, 0, 1, &cp);
   rt_flat_scene ft;  // the host octree's leaves (use_leaves)
@@ -180,14 +174,10 @@ extern "C" int rt_hip_cand_tile_entries(rt_hip_ctx* c, unsigned int* out, size_t
 }
 
 // ---------------------------------------------------- exact camera rays
-// Frame constants of the candidate lists (csrc/rt_cand.hip) and the three
-// launches: count -> scan -> (one small read-back for the list sizes) ->
-// fill.  Everything is derived from the frame in double, rounded so that
-// each bound stays conservative.
+// The builds of the candidate lists (launchers: csrc/rt_cand.h): count ->
+// scan -> (one small read-back for the list sizes) -> fill.
 // the headroom of the lists' entry and offset buffers (rt_mem.h half_more)
 static size_t list_room(size_t need) { return half_more(need, 8192); }
-
-static double d3dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 
 // big footprints whose per-lane row counts big_count_kernel keeps for
 // big_kernel (C5: ~5e4 per frame; beyond this big_kernel recounts)
@@ -198,7 +188,7 @@ static constexpr uint32_t kBigLaneCap = 1u << 17;
 #define RT_CAND_ITEM_CAP (1u << 20)
 #endif
 static constexpr uint32_t kItemCap = RT_CAND_ITEM_CAP;
-// (The lists' two prim-length scans are the device-length scan of rt_cand.hip:
+// (The lists' two prim-length scans are the device-length scan of rt_scan.h:
 // the classification's over the listed prims only, no zeroing pass.  rocPRIM's
 // scan over every prim with a separate scatter launch was removed.)
 
@@ -212,130 +202,6 @@ extern "C" int rt_hip_set_cand_item_cap(rt_hip_ctx* c, unsigned cap) {
 // the trace's item-clock sum in the frame counters (KParams::cost_sum)
 unsigned long long* cost_sum_of(rt_hip_ctx* c) {
   return (unsigned long long*)((char*)c->d_counter.get() + kItemCounterBytes + kStatBytes + kHitCounterBytes);
-}
-
-// Frame constants of the candidate lists for rank/nranks (no device work).
-int cand_params(const rt_frame* f, const float scene_c[3], float scene_r, float eps_ulps,
-                       double bound_scale, int rank, int nranks, CandParams* out, int compat) {
-  const double eps = 0x1p-24;
-  CandParams& cp = *out;
-  std::memset(&cp, 0, sizeof cp);
-  const double pos[3] = {f->position.x, f->position.y, f->position.z};
-  const double u[3] = {f->u.x, f->u.y, f->u.z}, v[3] = {f->v.x, f->v.y, f->v.z};
-  const double C[3] = {f->C.x, f->C.y, f->C.z};
-  double n[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-  const double nn = std::sqrt(d3dot(n, n));
-  if (!(nn > 1e-6)) return rt_set_error(RT_EINVAL, "degenerate camera (u parallel to v)");
-  for (int a = 0; a < 3; a++) {
-    cp.pos[a] = pos[a];
-    cp.u[a] = u[a];
-    cp.v[a] = v[a];
-    cp.C[a] = C[a];
-    cp.n[a] = n[a] / nn;
-  }
-  const double cpos[3] = {C[0] - pos[0], C[1] - pos[1], C[2] - pos[2]};
-  cp.plane = d3dot(cpos, cp.n);
-  if (!(std::fabs(cp.plane) > 1e-6)) return rt_set_error(RT_EINVAL, "degenerate camera (L = 0)");
-  const double g00 = d3dot(u, u), g01 = d3dot(u, v), g11 = d3dot(v, v);
-  const double det = g00 * g11 - g01 * g01;
-  cp.ginv[0] = g11 / det;
-  cp.ginv[1] = -g01 / det;
-  cp.ginv[2] = g00 / det;
-  cp.gscale = std::sqrt(cp.ginv[0] * cp.ginv[0] + 2 * cp.ginv[1] * cp.ginv[1] + cp.ginv[2] * cp.ginv[2]);
-  {
-    const double pc[3] = {-cpos[0], -cpos[1], -cpos[2]};
-    const double pu = d3dot(pc, u), pv = d3dot(pc, v);
-    cp.k0 = cp.ginv[0] * pu + cp.ginv[1] * pv;
-    cp.l0 = cp.ginv[1] * pu + cp.ginv[2] * pv;
-  }
-  // a tile's sample rectangle (rt_cand.hip tile_keep): cpu/rt's samples k in
-  // [W/2 - c, W/2 - c + 1/2] for the tile's columns c = 8 tx .. 8 tx + 7, so
-  // centre W/2 - 8 tx - 3.25 and half side 3.75 (likewise l); compatibility
-  // mode: k = c - W/2, centre 8 tx + 3.5 - W/2, half side 3.5
-  {
-    const double hw = (double)(f->width / 2), hh = (double)(f->height / 2);
-    cp.tile_hk = cp.tile_hl = compat ? 3.5 : 3.75;
-    cp.tile_k00 = compat ? 3.5 - hw : hw - 3.25;
-    cp.tile_l00 = compat ? 3.5 - hh : hh - 3.25;
-    cp.tile_dk = cp.tile_dl = compat ? 8.0 : -8.0;
-    for (int a = 0; a < 3; a++) {
-      cp.tile_p00[a] = pos[a] - (C[a] + cp.tile_k00 * u[a] + cp.tile_l00 * v[a]);
-      cp.tile_du[a] = cp.tile_dk * u[a];
-      cp.tile_dv[a] = cp.tile_dl * v[a];
-      cp.tile_w[a] = std::fabs(u[a]) * cp.tile_hk + std::fabs(v[a]) * cp.tile_hl;
-    }
-    cp.tile_hd = (cp.tile_hk * std::sqrt(d3dot(u, u)) + cp.tile_hl * std::sqrt(d3dot(v, v))) * (1.0 + 1e-12);
-  }
-  const int W = f->width, H = f->height;
-  cp.compat = compat;
-  if (compat) {
-    // gpu/rt: one sample per pixel of the 3x frame, k = px - W/2, px in
-    // [0, W - 1] (gpu/raytracer.cu:97-103), likewise l
-    cp.kmin = -(double)(W / 2);
-    cp.kmax = (double)(W - 1 - W / 2);
-    cp.lmin = -(double)(H / 2);
-    cp.lmax_ = (double)(H - 1 - H / 2);
-  } else {
-    // samples: k = i + {0, 1/2}, i in [1 - W/2, W/2] (cpu/raytracer.c:50-58)
-    cp.kmin = 1.0 - W / 2;
-    cp.kmax = W / 2 + 0.5;
-    cp.lmin = 1.0 - H / 2;
-    cp.lmax_ = H / 2 + 0.5;
-  }
-  double lmax = 0, omax = 0;
-  for (int ci = 0; ci < 4; ci++) {  // |o - pos| and |o| are convex: corners bound them
-    const double k = (ci & 1) ? cp.kmax : cp.kmin, l = (ci & 2) ? cp.lmax_ : cp.lmin;
-    double o[3], d[3];
-    for (int a = 0; a < 3; a++) {
-      o[a] = C[a] + u[a] * k + v[a] * l;
-      d[a] = o[a] - pos[a];
-    }
-    lmax = std::fmax(lmax, std::sqrt(d3dot(d, d)));
-    omax = std::fmax(omax, std::sqrt(d3dot(o, o)));
-  }
-  cp.lmax = lmax * (1 + 1e-9) + 1e-9;
-  cp.omax = omax * (1 + 1e-9) + 1e-9;
-  // float camera line (o_f, normalize(pos - o_f)): within 2.5 eps rad of the
-  // direction towards pos, so within dline of pos; o_f within dorig of o
-  cp.dline = 6.0 * eps * cp.lmax + 1e-12;
-  cp.dorig = 8.0 * eps * (std::sqrt(d3dot(C, C)) + std::fabs(cp.kmin) + cp.kmax + std::fabs(cp.lmin) +
-                          cp.lmax_) * 1.8;
-  // smallest culling slack of a camera ray: rt_cull_eps with the max-norm
-  // |o - c| bounded below per axis over the sample rectangle
-  double mlb = 0;
-  for (int a = 0; a < 3; a++) {
-    double lo = 1e300, hi = -1e300;
-    for (int ci = 0; ci < 4; ci++) {
-      const double k = (ci & 1) ? cp.kmax : cp.kmin, l = (ci & 2) ? cp.lmax_ : cp.lmin;
-      const double x = C[a] + u[a] * k + v[a] * l - scene_c[a];
-      lo = std::fmin(lo, x);
-      hi = std::fmax(hi, x);
-    }
-    const double m = (lo <= 0 && hi >= 0) ? 0.0 : std::fmin(std::fabs(lo), std::fabs(hi));
-    mlb = std::fmax(mlb, m);
-  }
-  const double R = scene_r;
-  const double cmag = std::fmax(std::fabs(scene_c[0]), std::fmax(std::fabs(scene_c[1]),
-                                                                std::fabs(scene_c[2])));
-  const double eps_rel = (double)(eps_ulps * kSlackUnit);
-  const double eps_min = (eps_rel * (std::fmax(mlb - cp.dorig, 0.0) + R) +
-                          (double)RT_CULL_PLANE * (cmag + R) + 1e-6) * (1.0 - 1e-5);
-  // the slab test's own rounding (rt_cull.h: a few ulps of |o| and of |t d|)
-  // takes 4 ulps of |o| + the scene's extent out of that slack
-  cp.eps_avail = eps_min - 8.0 * eps * (cp.omax + 2.0 * (cmag + R));
-  // tools/mt_bound.py: C_DOT = 6 sqrt 2 -> 8.6, C_A = 5 sqrt 2 -> 7.2 (scale 1 = the proven bound)
-  cp.c_dot = 8.6 * bound_scale;
-  cp.c_a = 7.2 * bound_scale;
-  cp.W = W;
-  cp.H = H;
-  cp.tiles_x = tiles_x_of(W);
-  cp.tiles_y = tiles_y_of(H);
-  cp.rank = rank;
-  cp.nranks = nranks;
-  cp.tb = rt_block_side(nranks);
-  cp.blocks_x = rt_blocks_x(cp.tiles_x, cp.tb);
-  cp.ntiles_local = rank_tile_count(W, H, rank, nranks);
-  return RT_OK;
 }
 
 // The last render's kept-entry count (rt_hip_stats reads it) outlives a list
@@ -377,8 +243,8 @@ static int cand_tile_buffers(rt_hip_ctx* c, size_t nt) {
 
 // The longest-first work order of the nt tiles from their offsets, and the
 // lists' kernel parameters common to both builds.
-static int cand_order(rt_hip_ctx* c, KParams* kp, size_t nt, uint32_t total, hipStream_t s, const rt_frame* f,
-                      int rank, int nranks) {
+static int cand_order(rt_hip_ctx* c, KParams* kp, size_t nt, hipStream_t s, const rt_frame* f, int rank,
+                      int nranks) {
   // the item clocks of this frame's last trace on this context (its counters
   // are zeroed only by the render that follows this order)
   // -- or of the last frame of the same size and rank split: a new camera
@@ -388,7 +254,7 @@ static int cand_order(rt_hip_ctx* c, KParams* kp, size_t nt, uint32_t total, hip
   const uint32_t* ic = hist ? c->d_item_cost : nullptr;
   const unsigned long long* cs = hist ? cost_sum_of(c) : nullptr;
   const auto order = [&](void* tmp, size_t* tb) {
-    return rt_cand_order(c->d_cand_start, (uint32_t)nt, total, c->d_order, c->d_order + nt + 1,
+    return rt_cand_order(c->d_cand_start, (uint32_t)nt, c->d_order, c->d_order + nt + 1,
                          c->d_order + 2 * (nt + 1), ic, cs, c->cost_waves, tmp, tb, s);
   };
   HIP_TRY(with_tmp(c->d_scan_tmp, order));
@@ -416,7 +282,7 @@ static int key_bits(size_t n_keys) {
 // Entries per big emission item for a build of 1/split of a frame's work (a
 // rank's lists of an N-rank frame, a producer's slice of N): 1024 for a whole
 // frame, halved per doubling of split down to 128, so the items stay many
-// enough to overlap (rt_cand.hip).  RT_CAND_CHUNK_SHIFT: A/B knob.
+// enough to overlap (rt_cand_passes.h).  RT_CAND_CHUNK_SHIFT: A/B knob.
 static uint32_t cand_chunk_shift(uint32_t split) {
   if (const char* e = std::getenv("RT_CAND_CHUNK_SHIFT")) {
     const int v = std::atoi(e);
@@ -664,7 +530,7 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   float* entry_skip = (float*)c->d_cand_keys2.get();
   HIP_TRY(rt_cand_entry_skip(c->d_cand, c->d_cand_skip, entry_skip, total, c->d_cand_start + nt, s));
   // longest-first work order of the rank's tiles (heavy lists first)
-  rc = cand_order(c, kp, nt, total, s, f, rank, nranks);
+  rc = cand_order(c, kp, nt, s, f, rank, nranks);
   if (rc) return rc;
   kp->cand = c->d_cand;
   kp->cand_global = c->d_cand_global;
@@ -805,7 +671,7 @@ extern "C" int rt_hip_cand_consume(rt_hip_ctx* c, const rt_frame* f, int rank, i
   HIP_TRY(rt_cand_gather(in, c->d_cand, (uint32_t)n, c->d_cand_vals, (float*)c->d_cand_keys.get(), s));
   KParams kp;
   std::memset(&kp, 0, sizeof kp);
-  rc = cand_order(c, &kp, nt, total, s, f, rank, nranks);
+  rc = cand_order(c, &kp, nt, s, f, rank, nranks);
   if (rc) return rc;
   c->ext = kp;
   c->ext.cand = c->d_cand_vals;

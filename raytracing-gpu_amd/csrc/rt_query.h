@@ -2,7 +2,7 @@
 // of walk for a closest hit (closest_q), the shadow query through a light's
 // buffer (LbRange, lbuf_range, lbuf_scan, lbuf_any; csrc/rt_lightbuf.hip) or
 // a walk (shadow_q), and the camera rays' candidate lists (cand_range,
-// cand_closest; csrc/rt_cand.hip).
+// cand_closest; built by csrc/rt_cand.hip).
 // Part of rt_render.hip's one translation unit.  Needs rt_walk_lane.h and
 // rt_walk_wave.h (included here).
 #pragma once
@@ -347,7 +347,7 @@ __device__ __forceinline__ void cand_closest(const KParams& p, const Ray& r, boo
                                              Best& b, WaveCtx& w, WorkCount& wc) {
   if (!p.cand_start || __ballot(act) == 0) return;
     // Depth skip: a candidate's float new_dist is at least |pos - o| + its
-    // entry's cand_skip (csrc/rt_cand.hip), so one whose bound exceeds every
+    // entry's cand_skip (csrc/rt_cand_geom.h Footprint::skip), so one whose bound exceeds every
     // lane's best - |pos - o| (plus the float error of that difference)
     // cannot win here -- one compare instead of a test.  (A per-lane test of
     // the footprint's image-space band, measured: the bands of the long

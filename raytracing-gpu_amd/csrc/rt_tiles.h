@@ -1,7 +1,7 @@
 // rt_tiles.h -- how the frame's 8x8-pixel tiles are dealt to ranks, shared
 // by the device kernels (render, candidate lists, assemble) and their host
-// mirrors (rt_hip.cpp, the host re-derivation of the candidate lists,
-// rtgpu.py's tile_xy / tile_local).
+// mirrors (rt_hip.cpp, the host re-derivation of the candidate lists in
+// rt_cand_host.cpp, rtgpu.py's tile_xy / tile_local).
 //
 // Tiles are grouped into blocks of tb x tb tiles, tb = rt_block_side(nranks):
 // 4 (32 x 32 pixels) when the frame is split, 1 (plain scanline tile order)
@@ -10,7 +10,7 @@
 // blocks in scanline order, each as tb^2 tiles in row-major order (tiles past
 // the frame's edge are padding: their pixels are invalid and written as 0).
 //
-// Why whole blocks: a camera-ray candidate footprint (csrc/rt_cand.hip) of a
+// Why whole blocks: a camera-ray candidate footprint (csrc/rt_cand_geom.h) of a
 // few tiles touches one or two ranks instead of one rank per 8-pixel column
 // (round 2's interleave t mod n made every rank classify every footprint
 // wider than 8 n pixels).  Why diagonals: rounds 3-4 dealt block b (scanline)
@@ -66,6 +66,17 @@ RT_TILES_FN uint32_t rt_rank_rows_blocks(uint32_t by, uint32_t blocks_x, uint32_
 // blocks of rank r in a frame of blocks_x x blocks_y blocks
 RT_TILES_FN uint32_t rt_rank_blocks(uint32_t blocks_x, uint32_t blocks_y, uint32_t n, uint32_t r) {
   return rt_rank_rows_blocks(blocks_y, blocks_x, n, r);
+}
+
+// tiles per row and per column of a W x H frame (a ragged edge is a whole tile)
+RT_TILES_FN int tiles_x_of(int W) { return (W + 7) / 8; }
+RT_TILES_FN int tiles_y_of(int H) { return (H + 7) / 8; }
+
+// tiles rank `rank` renders (whole blocks, edge padding included)
+RT_TILES_FN int rank_tile_count(int W, int H, int rank, int nranks) {
+  const int tb = rt_block_side(nranks);
+  return (int)(rt_rank_blocks((uint32_t)rt_blocks_x(tiles_x_of(W), tb), (uint32_t)rt_blocks_y(tiles_y_of(H), tb),
+                              (uint32_t)nranks, (uint32_t)rank) * tb * tb);
 }
 
 // the most blocks any rank holds (the tile buffers' stride; host side, O(n))

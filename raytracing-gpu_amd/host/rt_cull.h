@@ -37,6 +37,9 @@
 #define RT_CULL_TREL 4.76837158203125e-7f
 /* 2^-22 x (|scene centre| + R): rounding of the grown box planes themselves */
 #define RT_CULL_PLANE 2.384185791015625e-7f
+/* The unit of the culling slacks: eps_ulps of them, relative to the
+ * origin-to-geometry distance (2^-24; DESIGN.md "Conservative culling"). */
+static const float kSlackUnit = 5.9604645e-8f;
 
 /* eps_rel = ulps * 2^-24; (dx,dy,dz) = origin - scene centre; cmag =
  * max-norm of the scene centre; R = scene half-extent (max-norm). */

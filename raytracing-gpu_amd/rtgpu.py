@@ -409,13 +409,13 @@ def accel_probe(scene, accel="octree", stride=97, check=True):
 
 def cand_survey(scene, eps_ulps=64.0, bound_scale=1.0, threads=8, leaves=False):
     """Host-only: {safe, footprint, global, entries} of the camera candidate
-    lists of the scene's frame (csrc/rt_cand.hip classify + raster)."""
+    lists of the scene's frame (csrc/rt_cand_geom.h classify + raster, run by csrc/rt_cand_host.cpp)."""
     out = (C.c_ulonglong * 88)()
     _check(lib().rt_cand_survey(scene.ptr, eps_ulps, bound_scale, threads, 1 if leaves else 0, out),
            "cand_survey")
     r = dict(zip(("safe", "footprint", "global", "entries"), (int(x) for x in out[:4])))
     # the entries the device lists hold with the per-tile refinement (big
-    # footprints refined, csrc/rt_cand.hip tile_keep); the big footprints'
+    # footprints refined, csrc/rt_cand_geom.h tile_keep); the big footprints'
     # entries before and after it
     r["refined"] = int(out[68])
     r["big_entries"], r["big_kept"] = int(out[69]), int(out[70])
@@ -434,7 +434,7 @@ def cand_survey(scene, eps_ulps=64.0, bound_scale=1.0, threads=8, leaves=False):
 
 def cand_refine_sample(scene, stride=1, cap=1 << 20, eps_ulps=64.0, bound_scale=1.0, compat=False):
     """Host-only: every stride-th entry of the refined candidate footprints
-    as rows (prim, tile x, tile y, kept) -- csrc/rt_cand.hip tile_keep -- and
+    as rows (prim, tile x, tile y, kept) -- csrc/rt_cand_geom.h tile_keep -- and
     the number sampled (compat: the gpu/rt mode's 3x frame)."""
     import numpy as np
     out = np.zeros((cap, 4), np.uint32)

@@ -147,7 +147,7 @@ def _a2a_worker(rank, world, store, q):
     sys.path.insert(0, os.path.join(REPO, "raytracing-gpu_amd"))
     import rtgpu
     dist.init_process_group("gloo", init_method="file://" + store, rank=rank, world_size=world)
-    # what every producer r routes to every rank d (csrc/rt_cand.hip pack
+    # what every producer r routes to every rank d (csrc/rt_cand_entries.h pack
     # format: local tile or tpr, prim, skip bits), deterministic per (r, d)
     def block(r, d):
         rng = np.random.default_rng(1000 * r + d)
@@ -184,7 +184,7 @@ def test_triangle_parallel_list_exchange_gloo(world, tmp_path):
 @pytest.mark.parametrize("size,n", [((3840, 2160), 8), ((3840, 2160), 4), ((1920, 1080), 3), ((96, 54), 8),
                                     ((640, 360), 2)])
 def test_triangle_parallel_route_keys(size, n):
-    """The routing of rt_hip_cand_produce (csrc/rt_cand.hip route_kernel,
+    """The routing of rt_hip_cand_produce (csrc/rt_cand_entries.h route_key,
     mirrored with rtgpu.tile_local): every scanline tile of the one-rank build
     maps to one (rank, local tile) with local < tpr, so the key
     rank * (tpr + 1) + local is unique, below nranks * (tpr + 1), sorts by rank

@@ -1,6 +1,6 @@
-"""Exact camera rays (csrc/rt_cand.hip): the forward error
-bound of the reference's float Moller-Trumbore test and the host mirror of
-the per-frame candidate lists.  CPU only."""
+"""Exact camera rays (csrc/rt_cand_geom.h): the forward error
+bound of the reference's float Moller-Trumbore test and the host mirrors of
+the per-frame candidate lists (csrc/rt_cand_host.cpp).  CPU only."""
 import os
 import sys
 
@@ -91,7 +91,7 @@ def test_candidate_survey_reference_scene(scene_dir):
 
 @pytest.mark.parametrize("case", ["small", "c5", "474x266", "266x476"])
 def test_tile_refinement_drops_only_tiles_the_reference_never_accepts(case):
-    """The per-tile refinement of the camera candidate lists (csrc/rt_cand.hip
+    """The per-tile refinement of the camera candidate lists (csrc/rt_cand_geom.h
     tile_keep) drops a (triangle, tile) entry only where its proof says no
     camera sample of the tile can pass the float test.  Checked against the
     oracle's restatement of cpu/hit.c:15-44 on every camera sample

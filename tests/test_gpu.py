@@ -528,7 +528,7 @@ def test_exact_camera_rank_split(gpu):
                                                         ("octree_gpu", 1, (0,), 0),
                                                         ("octree_gpu", 3, (0, 2), 5)])
 def test_candidate_lists_match_host(gpu, accel, nranks, ranks, item_cap):
-    """The device-built camera candidate lists (csrc/rt_cand.hip: float fast
+    """The device-built camera candidate lists (csrc/rt_cand_passes.h: float fast
     path, f64 classification, small/big footprint split, emission, radix
     sort, per-tile offsets) equal the host re-derivation from the same
     classify/raster code: every listed prim's footprint bit for bit, every
@@ -1035,7 +1035,7 @@ def test_compat_full_frame_octree_vs_flat(gpu, accel):
     """gpu/rt compatibility mode over a whole frame of a million-triangle
     synthetic scene (10 x 10 spheres of 9,776 triangles + ground, 320 x 180
     output = 960 x 540 rays): the octree walk with the compat camera's
-    candidate lists (csrc/rt_cand.hip CandParams::compat) equals brute force
+    candidate lists (csrc/rt_cand.h CandParams::compat) equals brute force
     (RT_ACCEL_FLAT, the restated gpu/hit.cu test over every triangle) byte
     for byte -- grazing camera rays whose float garbage hit lies beyond the
     walk's slack included (/root/reference/gpu/raytracer.cu:87-129)."""
@@ -1297,7 +1297,7 @@ def test_light_buffer_entries_match_host_survey(gpu, exact):
 @pytest.mark.parametrize("accel", ["octree_gpu", "octree"])
 def test_camera_refine_on_off(gpu, accel):
     """The per-tile refinement of the candidate lists (rt_hip_set_camera_refine,
-    csrc/rt_cand.hip tile_keep) only drops entries no camera ray of their tile
+    csrc/rt_cand_geom.h tile_keep) only drops entries no camera ray of their tile
     can accept: the frame is bit-identical with it off, with fewer entries on;
     the host re-derivation matches the device lists both ways (the host applies
     the same refinement), N = 1 and rank 2 of 3."""

@@ -17,7 +17,7 @@ satisfy U >= -du, V >= -dv, U + V <= 1 + dw with
     rho = E_a / a_lb,  du = E_sh / (a_lb (1 - rho)),  dv = E_dq / (a_lb (1 - rho)),
     dw = (4 eps + (E_sh + E_dq) / a_lb + rho) / (1 - rho)
 for any lower bound a_lb <= |a| (at least 1e-7f, since smaller |a| is
-rejected).  csrc/rt_cand.hip evaluates exactly these formulas per triangle
+rejected).  csrc/rt_cand_geom.h (classify) evaluates exactly these formulas per triangle
 for the camera rays; this script checks them against the
 float test itself on grazing rays.
 
@@ -89,7 +89,7 @@ def exact_bary(o, d, v0, e1, e2):
 
 
 def bound_cw(o, d, v0, e1, e2, a_lb):
-    """Componentwise version (csrc/rt_cand.hip second round):
+    """Componentwise version (csrc/rt_cand_geom.h classify, second round):
     E_sh <= 6.01 eps sum |S_i| M_i, M_i = |d_j| |e2_k| + |d_k| |e2_j|;
     E_dq <= 6.01 eps sum |d_i| N_i, N_i = |S_j| |e1_k| + |S_k| |e1_j|;
     E_a <= 5.01 eps sum |e1_i| M_i.  Returns (du, dv, dw)."""
