@@ -115,7 +115,8 @@ constexpr uint32_t RT_KEPT_COUNT = 0, RT_KEPT_CTR = 1, RT_KEPT_WORDS = RT_KEPT_C
 constexpr int rt_rstart_ctr(int nranks) { return nranks + 1; }
 constexpr int rt_rstart_words(int nranks) { return rt_rstart_ctr(nranks) + (int)RT_CC_BUILD_WORDS; }
 
-// ---- light-buffer build counters (rtl::BP::ctr, rt_lightbuf.hip)
+// ---- light-buffer build counters (rtl::BP::ctr, rt_lightbuf.hip; row_entries
+// of rt_lightbuf_geom.h sets RT_LBC_OVERFLOW)
 enum RtLbCtr : uint32_t {
   RT_LBC_BIG = 0,       // big-footprint prims (counted and emitted row-wise by a workgroup)
   RT_LBC_GLOBAL = 1,    // global prims (every shadow ray of the light tests them)

@@ -1,7 +1,9 @@
 // rt_ctx.h -- the device context (rt_hip_ctx) shared by the host side of the
 // C ABI (include/rt_hip.h, include/rt_hip_test.h), split by concern:
-//   rt_hip.cpp     context lifetime, settings, light buffers, render, stats,
-//                  assemble, the gpu/rt compatibility mode, rt_raytrace
+//   rt_hip.cpp     context lifetime, settings, light buffers (their build
+//                  parameters: rt_lightbuf_host.cpp lb_fill, which needs no
+//                  context), render, stats, assemble, the gpu/rt
+//                  compatibility mode, rt_raytrace
 //   rt_lists.cpp   the camera rays' candidate lists (per rank and
 //                  triangle-parallel produce / consume) and the entry points
 //                  of their host mirrors (rt_cand_host.cpp, which needs no context)
@@ -305,8 +307,6 @@ static inline void scene_extent(const rt_flat_scene& fs, float c[3], float* r) {
 
 // shared between the files above (defined in the file named)
 int shadow_prepare(rt_hip_ctx* c, hipStream_t s);                                  // rt_hip.cpp
-void lb_fill(LBParams& lp, const float scene_c[3], float scene_r, const float aabb_lo[3], const float aabb_hi[3],
-             float eps_ulps, uint32_t type, const float lv[3], uint32_t nprim, int proven);  // rt_hip.cpp
 int lbuf_prepare(rt_hip_ctx* c, hipStream_t s);                                    // rt_hip.cpp
 int reflect_prepare(rt_hip_ctx* c, hipStream_t s);                                 // rt_hip.cpp
 int choose_accel(const rt_scene* s);                                               // rt_hip.cpp

@@ -112,61 +112,6 @@ static void lbuf_release(rt_hip_ctx* c) {
   c->lb_ulps = -1.0f;
 }
 
-// The build parameters of one light's buffer for a scene of nprim triangles
-// in the box (scene_c, scene_r) and the culling slack eps_ulps.
-void lb_fill(LBParams& lp, const float scene_c[3], float scene_r, const float aabb_lo[3],
-                    const float aabb_hi[3], float eps_ulps, uint32_t type, const float lv[3], uint32_t nprim,
-                    int proven) {
-  std::memset(&lp, 0, sizeof lp);
-  // a shadow ray leaves a hit point: inside the scene cube up to the float
-  // error of the hit, so its slack eps(o) (host/rt_cull.h, float) is at most
-  const double R = scene_r, eps_rel = (double)(eps_ulps * kSlackUnit);
-  const double cmag = std::fmax(std::fabs(scene_c[0]), std::fmax(std::fabs(scene_c[1]), std::fabs(scene_c[2])));
-  const double slack = (eps_rel * (2.0 * R * 1.001 + 1e-3) + (double)RT_CULL_PLANE * (cmag + R) + 1e-6) * 1.01;
-  double lo[3], hi[3], s1 = 0.0;
-  for (int a = 0; a < 3; a++) {
-    if (proven) {
-      // the proof's origin box: the triangles' box grown by 1 + 1 % of the
-      // scene (hit points off it -- float garbage hits beyond that -- are
-      // counted by the shade pass, never assumed)
-#ifndef RT_LB_PROOF_BOX
-#define RT_LB_PROOF_BOX 1.0  // the proof box: the triangles' box grown by g = RT_LB_PROOF_BOX (1 + 0.02 R)
-#endif
-      const double g = RT_LB_PROOF_BOX * (1.0 + 0.02 * R);
-      lo[a] = (double)aabb_lo[a] - g;
-      hi[a] = (double)aabb_hi[a] + g;
-    } else {
-      lo[a] = scene_c[a] - R * 1.001 - 1e-3;
-      hi[a] = scene_c[a] + R * 1.001 + 1e-3;
-    }
-    s1 += std::fmax(std::fabs(lo[a]), std::fabs(hi[a]));
-  }
-  lp.nprim = nprim;
-  lp.kind = type == 1 ? RT_LB_DIR : RT_LB_POINT;
-  double dmax = 0.0;
-  for (int a = 0; a < 3; a++) {
-    lp.lv[a] = lv[a];
-    lp.box_lo[a] = lo[a];
-    lp.box_hi[a] = hi[a];
-  }
-  for (int k = 0; k < 8; k++) {
-    double d2 = 0.0;
-    for (int a = 0; a < 3; a++) {
-      const double x = ((k >> a) & 1 ? hi[a] : lo[a]) - lp.lv[a];
-      d2 += x * x;
-    }
-    dmax = std::fmax(dmax, std::sqrt(d2));
-  }
-  lp.slack = slack;
-  lp.s1 = s1;
-  lp.dmax = dmax * 1.01 + 1.0;
-  // two cells per triangle: C5 shade 1.97 -> 1.93 ms against one (half: 2.12,
-  // four: 2.09; 117 M -> 172 M proven entries, 8 GB; profiles/r05x_tuning/)
-  const uint64_t cells = 2ull * nprim;
-  lp.target_cells = cells < 4096u ? 4096u : (cells > (1u << 25) ? (1u << 25) : (uint32_t)cells);
-  lp.proven = proven ? 1u : 0u;
-}
-
 // The buffer of light li (lb_dev[li] is null, lb_host / lb_failed hold nlight
 // entries) for the context's slack and mode; a light that casts no shadow has
 // none.  RT_OK also when the build fell back to the walk (lb_failed[li]); an

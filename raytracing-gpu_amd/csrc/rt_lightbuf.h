@@ -62,23 +62,51 @@ struct LBParams {
   uint64_t max_entries;
 };
 
+// The slots of a host survey (rt_lightbuf_survey_host; include/rt_hip_test.h
+// rt_lightbuf_survey hands them out by number).
+enum RtLbSurvey : uint32_t {
+  RT_LBS_ENTRIES = 0,             // entries
+  RT_LBS_NEVER = 1,               // prims never accepted
+  RT_LBS_GLOBAL = 2,              // global prims
+  RT_LBS_BAND = 3,                // band prims
+  RT_LBS_BIG = 4,                 // big prims (a band, or more than 1024 cells)
+  RT_LBS_PRIMS = 5,               // prims surveyed
+  RT_LBS_BAND_ENTRIES = 6,        // entries in band rows
+  RT_LBS_MAX_COUNT = 7,           // the largest per-prim count
+  RT_LBS_MAX_PRIM = 8,            // its prim
+  RT_LBS_ENTRIES_OVER_1024 = 9,   // entries of prims with more than 1024
+  RT_LBS_ENTRIES_65_1024 = 10,    // entries of prims with 65 .. 1024
+  RT_LBS_PRIMS_OVER_64 = 11,      // prims with more than 64 entries
+  RT_LBS_WORDS = 12
+};
+
 struct LBDevice;  // device allocations of one light's buffer (rt_lightbuf.hip)
 
+// ---- rt_lightbuf.hip: the device build
 // Build one light's buffer on the stream (synchronous at the end: the entry
 // count sizes the sort).  *out is filled with device pointers owned by *dev.
+// 1 with err filled: no buffer for want of capacity (device memory, the entry
+// and cell caps, a zero directional vector); -1: anything else.  On failure
+// *out is zeroed and *dev is null.
 extern "C" int rt_lightbuf_build(const LBParams* p, RtLightBuf* out, LBDevice** dev, hipStream_t s,
                                  char* err, size_t errlen);
 extern "C" void rt_lightbuf_free(LBDevice* dev);
 // entries and cells of a built buffer (bench / info)
 extern "C" void rt_lightbuf_sizes(const LBDevice* dev, unsigned long long* entries,
                                   unsigned long long* cells, unsigned long long* global);
-// The same footprints counted on the host (in->tri = host prim-order
-// records), every stride-th prim: out[0] entries, [1] never accepted, [2]
-// global, [3] band prims, [4] big prims, [5] prims surveyed, [6] band-row
-// entries, [7] largest per-prim count, [8] its prim.
-extern "C" int rt_lightbuf_survey_host(const LBParams* in, uint32_t stride, unsigned long long out[12],
-                                       char* err, size_t errlen);
 // proven mode: triangles no ray of the light can make the float test accept
 // (skipped), and triangles listed along a band of the cube map (point lights)
 extern "C" void rt_lightbuf_proof_counts(const LBDevice* dev, unsigned long long* never,
                                          unsigned long long* band);
+
+// ---- rt_lightbuf_host.cpp: plain C++, no device (lb_derive_grid and
+// lb_geom_host, which fill rtl::LbGeom, are declared in rt_lightbuf_geom.h)
+// The build parameters of one light's buffer (tri and max_entries left zero)
+// for a scene of nprim triangles in the box (scene_c, scene_r) with the
+// triangles' own box (aabb_lo, aabb_hi) and the culling slack eps_ulps.
+void lb_fill(LBParams& lp, const float scene_c[3], float scene_r, const float aabb_lo[3], const float aabb_hi[3],
+             float eps_ulps, uint32_t type, const float lv[3], uint32_t nprim, int proven);
+// The same footprints counted on the host (in->tri = host prim-order
+// records), every stride-th prim, into out[RtLbSurvey].
+extern "C" int rt_lightbuf_survey_host(const LBParams* in, uint32_t stride, unsigned long long out[RT_LBS_WORDS],
+                                       char* err, size_t errlen);

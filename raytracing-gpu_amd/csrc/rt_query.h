@@ -1,12 +1,14 @@
 // rt_query.h -- the queries the kernels ask: the traversal policy's choice
 // of walk for a closest hit (closest_q), the shadow query through a light's
-// buffer (LbRange, lbuf_range, lbuf_scan, lbuf_any; csrc/rt_lightbuf.hip) or
+// buffer (LbRange, lbuf_range, lbuf_scan, lbuf_any; built by
+// csrc/rt_lightbuf.hip, the cells a ray looks up: csrc/rt_lightbuf_cell.h) or
 // a walk (shadow_q), and the camera rays' candidate lists (cand_range,
 // cand_closest; built by csrc/rt_cand.hip).
 // Part of rt_render.hip's one translation unit.  Needs rt_walk_lane.h and
 // rt_walk_wave.h (included here).
 #pragma once
 
+#include "rt_lightbuf_cell.h"
 #include "rt_walk_lane.h"
 #include "rt_walk_wave.h"
 
@@ -84,7 +86,8 @@ __device__ __forceinline__ void closest_q(const KParams& p, const Ray& r, bool a
   }
 }
 
-// Shadow query through the light's buffer (csrc/rt_lightbuf.hip): the
+// Shadow query through the light's buffer (built by csrc/rt_lightbuf.hip; the
+// listing it relies on: csrc/rt_lightbuf_geom.h): the
 // triangles listed in the cell the ray's origin projects to, in key order,
 // up to the first any-hit -- for a point light also the opposite cell, whose
 // triangles lie beyond the light (cpu/rt's shadow ray does not stop there,
@@ -99,49 +102,7 @@ struct LbRange {
 __device__ __forceinline__ LbRange lbuf_range(const RtLightBuf& L, const Ray& r) {
   uint32_t cell[2] = {0xffffffffu, 0xffffffffu};
   float lim = __builtin_inff();  // key limit of cell[0] (cell[1]: none)
-  if (L.kind == RT_LB_DIR) {
-    // the same float operations the build's margins assume (no contraction)
-    const float pu = r.o.x * L.u[0] + r.o.y * L.u[1] + r.o.z * L.u[2];
-    const float pv = r.o.x * L.v[0] + r.o.y * L.v[1] + r.o.z * L.v[2];
-    const float pw = r.o.x * L.w[0] + r.o.y * L.w[1] + r.o.z * L.w[2];
-    const float fx = (pu - L.u0) * L.inv_cs, fy = (pv - L.v0) * L.inv_cs;
-    if (fx >= 0.0f && fy >= 0.0f && fx < (float)L.nx && fy < (float)L.ny) {
-      cell[0] = (uint32_t)fy * L.nx + (uint32_t)fx;
-      lim = -pw;  // keys are minus the triangles' depth bounds toward the light
-    }
-  } else {
-    // from the light to the origin: -d, the ray's own direction negated
-    const f3 x{-r.d.x, -r.d.y, -r.d.z};
-    const float ax = fabsf(x.x), ay = fabsf(x.y), az = fabsf(x.z);
-    uint32_t a = 0;
-    float m = ax, xa = x.x, xj = x.y, xk = x.z;
-    if (ay > m) {
-      a = 1;
-      m = ay;
-      xa = x.y;
-      xj = x.z;
-      xk = x.x;
-    }
-    if (az > m) {
-      a = 2;
-      m = az;
-      xa = x.z;
-      xj = x.x;
-      xk = x.y;
-    }
-    if (m > 0.0f) {
-      const uint32_t n = L.nx;
-      const float sc = xj / m, tc = xk / m;
-      const uint32_t f = 2u * a + (xa < 0.0f ? 1u : 0u);
-      const uint32_t ix = min((uint32_t)((sc + 1.0f) * L.half_n), n - 1u);
-      const uint32_t iy = min((uint32_t)((tc + 1.0f) * L.half_n), n - 1u);
-      const uint32_t jx = min((uint32_t)((1.0f - sc) * L.half_n), n - 1u);
-      const uint32_t jy = min((uint32_t)((1.0f - tc) * L.half_n), n - 1u);
-      cell[0] = (f * n + iy) * n + ix;
-      cell[1] = ((f ^ 1u) * n + jy) * n + jx;
-      lim = length(x) * (1.0f + 1e-6f);  // keys: nearest distance from the light
-    }
-  }
+  lbuf_cells(L, r.o, r.d, cell, lim);  // rt_lightbuf_cell.h
   // both cells' entry ranges (independent loads)
   LbRange g;
   g.lim = lim;

@@ -6,7 +6,7 @@
 // surface and may point anywhere, so no per-frame or per-light family bounds
 // its cosine with a triangle's plane, as the eye does for camera rays
 // (csrc/rt_cand.hip) and the lights do for shadow rays (csrc/rt_shadow.hip,
-// csrc/rt_lightbuf.hip).  The bound of tools/mt_bound.py still holds for any
+// csrc/rt_lightbuf_geom.h).  The bound of tools/mt_bound.py still holds for any
 // ray: a float accept (cpu/hit.c:15-33) implies the exact line crosses the
 // triangle's plane at X inside the expanded triangle T_D, whose reach beyond
 // the triangle is

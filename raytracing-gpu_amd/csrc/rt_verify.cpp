@@ -64,9 +64,10 @@ extern "C" int rt_tile_map_check(int width, int height, int nranks, int maxw, un
 
 // Host-only survey of a light's buffer as rt_hip_create would build it for
 // this scene (prim-order records, the scene's box, the default culling
-// slack): rt_lightbuf_survey_host's counts (csrc/rt_lightbuf.h).
+// slack): rt_lightbuf_survey_host's counts (csrc/rt_lightbuf.h RtLbSurvey).
+static_assert(RT_LBS_WORDS == 12, "include/rt_hip_test.h promises out[12]");
 extern "C" int rt_lightbuf_survey(const rt_scene* scene, unsigned light, int exact, unsigned stride,
-                                  unsigned long long out[12]) {
+                                  unsigned long long out[RT_LBS_WORDS]) {
   if (!scene || !out) return rt_set_error(RT_EINVAL, "null argument");
   if (light >= scene->light_count || (scene->lights[light].type != 1 && scene->lights[light].type != 2))
     return rt_set_error(RT_EINVAL, "light %u is not a directional or point light", light);

@@ -18,6 +18,7 @@
 
 #include "rt_cull.h"
 #include "rt_internal.h"
+#include "rt_mt.h"
 
 typedef struct { float dist; uint32_t prim; rt_vec3 pt; } winner;
 
@@ -35,27 +36,6 @@ static float probe_box_enter(rt_vec3 o, rt_vec3 inv, float eps, float lx, float 
 static int rt_prune(float t_enter, float dlen, float best, float eps)
 {
   return t_enter * dlen > rt_prune_limit(best, eps);
-}
-
-static int mt_exact(rt_vec3 o, rt_vec3 d, const float *r, float *t, float *u, float *v)
-{
-  const float eps = 0.0000001f;
-  rt_vec3 v0 = { r[0], r[1], r[2] }, e1 = { r[3], r[4], r[5] }, e2 = { r[6], r[7], r[8] };
-  rt_vec3 h = rt_v_cross(d, e2);
-  float a = e1.x * h.x + e1.y * h.y + e1.z * h.z;
-  if (a > -eps && a < eps)
-    return 0;
-  float f = 1 / a;
-  rt_vec3 s = rt_v_sub(o, v0);
-  *u = f * (s.x * h.x + s.y * h.y + s.z * h.z);
-  if (*u < 0.0 || *u > 1.0)
-    return 0;
-  rt_vec3 q = rt_v_cross(s, e1);
-  *v = f * (d.x * q.x + d.y * q.y + d.z * q.z);
-  if (*v < 0.0 || *u + *v > 1.0)
-    return 0;
-  *t = f * (e2.x * q.x + e2.y * q.y + e2.z * q.z);
-  return *t > eps;
 }
 
 static void consider(rt_vec3 o, rt_vec3 d, rt_vec3 nd, float dlen, const float *r, winner *w)

@@ -6,8 +6,9 @@
 // that spelled the words by number (985109c): rt_hip_stats' 23 `out->x = h[n]`
 // lines, shade_stat_slot's set, fold_kernel's frame check, the comment at
 // CandParams::ctr with d_cand_ctr's `+ 8` / `+ 16` / 32, and rt_lightbuf_build's
-// hc[0..4].  The kernels' assembly says the device side kept its numbers;
-// this says the names mean what the numbers meant.
+// hc[0..4] (csrc/rt_lightbuf.hip; the emission's overflow flag is set in
+// csrc/rt_lightbuf_geom.h row_entries).  The kernels' assembly says the device
+// side kept its numbers; this says the names mean what the numbers meant.
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
