@@ -6,11 +6,17 @@
 // (included here: the box tests, kLdsStack for the shared stack area).
 #pragma once
 
+#include "rt_push_plan.h"
 #include "rt_walk_lane.h"
 
 namespace rt {
 
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+// the compare's own scalar pair (__ballot goes through a select and a second compare)
+__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// v_writelane_b32: `old` with lane `l` (wave-uniform) replaced by the wave-uniform x.  clang has
+// no builtin of that name; the declaration binds the LLVM intrinsic itself.
+__device__ int wave_writelane(int x, int l, int old) __asm("llvm.amdgcn.writelane");
 // Wave-uniform loads through the constant address space: with a uniform
 // address they become scalar (SMEM) loads straight into SGPRs.  The scene
 // image is read-only for the whole launch.
@@ -288,49 +294,61 @@ __device__ bool flat_any_tp(const KParams& p, const Ray& r, bool act, WorkCount&
 
 // Interior node whose child boxes are staged: test them, push the ones any
 // lane wants (with the mask of the lanes that want each) far-to-near in
-// octant order, so the nearest child ends on top of the stack.
+// octant order, so the nearest child ends on top of the stack.  The pushes
+// are one vector step, not a loop over the octants: which slot each child
+// takes is a function of the wave-uniform mask, dm and the children's
+// ballots alone (csrc/rt_push_plan.h), and the stack ends up byte for byte
+// what the serial loop left.
 template <bool ANY>
 __device__ __forceinline__ void stage_push_children(const Ray& r, f3 inv, uint32_t dm,
                                                     uint32_t info, bool want, float limit,
                                                     int& sp, WaveCtx& w, WorkCount& wc,
                                                     const float2* __restrict__ mu = nullptr) {
-  uint32_t mask = RT_NODE_MASK(info), cnt = RT_NODE_COUNT(info);
-  uint64_t lanes[8];
-  uint32_t hitmask = 0;
+  const uint32_t mask = RT_NODE_MASK(info), cnt = RT_NODE_COUNT(info);
+  // lane c keeps the mask of the lanes that want child c (v_writelane of the
+  // compares' own scalar pairs): the ballots never sit in scalar registers
+  // past their own child's test
+  int wlo = 0, whi = 0;
+  const uint64_t wm = wave_ballot(want);
 #pragma unroll
   for (int c = 0; c < 8; c++) {
-    lanes[c] = 0;
     if ((uint32_t)c < cnt) {
       float4 clo = w.stage[2 * c], chi = w.stage[2 * c + 1];
-      bool w2;
+      uint64_t bc;
       if (ANY) {
-        w2 = want && (mu ? box_hit_sh(r, inv, clo, chi, mu[c])  // exact-shadow mode's grown boxes
-                         : box_enter(r, inv, clo, chi) != __builtin_inff());
+        bc = wm & (mu ? wave_ballot(box_hit_sh(r, inv, clo, chi, mu[c]))  // exact-shadow mode's grown boxes
+                      : wave_ballot(box_enter(r, inv, clo, chi) != __builtin_inff()));
       } else {
         float t0 = box_enter(r, inv, clo, chi);
-        w2 = want && t0 != __builtin_inff() && !(t0 * r.dlen > limit);
+        bc = wm & wave_ballot(t0 != __builtin_inff()) & wave_ballot(!(t0 * r.dlen > limit));
       }
-      lanes[c] = __ballot(w2);
-      if (lanes[c] != 0) hitmask |= 1u << c;
+      wlo = wave_writelane((int)(uint32_t)bc, c, wlo);
+      whi = wave_writelane((int)(uint32_t)(bc >> 32), c, whi);
     }
   }
-  for (int j = 7; j >= 0; --j) {
-    uint32_t o = (uint32_t)j ^ dm;
-    if (!(mask & (1u << o))) continue;
-    uint32_t c = (uint32_t)__popc(mask & ((1u << o) - 1u));
-    if (!(hitmask & (1u << c))) continue;
-    if (sp < kStack2) {
-      if (w.lane < 2) w.stk2[2 * sp + w.lane] = w.stage[2 * c + w.lane];
-      uint64_t lm = 0;
-#pragma unroll
-      for (int k = 0; k < 8; k++)
-        if ((uint32_t)k == c) lm = lanes[k];
-      if (w.lane == 0) w.stkm[sp] = lm;
-      sp++;
-    } else {
-      wc.overflow++;  // RT_EDEPTH, never silent
-    }
+  // One push step for the whole node (csrc/rt_push_plan.h): lane k < 8 takes
+  // push-order key k, fetches its child's lane mask from lane `child` and the
+  // child's record from the stage in one LDS round trip, and stores both at
+  // its own slot.  The slots, sp and the overflow count are the serial
+  // far-to-near loop's.
+  const RtPushLane pl = rt_push_lane(mask, dm, (uint32_t)w.lane);
+  const uint32_t mlo = (uint32_t)__shfl(wlo, (int)pl.child), mhi = (uint32_t)__shfl(whi, (int)pl.child);
+  float4 rlo, rhi;
+  if (w.lane < 8) {  // child <= 8: inside the stage whatever the key
+    rlo = w.stage[2 * pl.child];
+    rhi = w.stage[2 * pl.child + 1];
   }
+  const bool push = w.lane < 8 && rt_push_wanted(pl, ((mlo | mhi) != 0 ? 1u : 0u) << pl.child);
+  const uint32_t B = (uint32_t)wave_ballot(push);
+  const int slot = sp + (int)rt_push_rank(B, (uint32_t)w.lane);
+  if (push && slot < kStack2) {
+    w.stk2[2 * slot] = rlo;
+    w.stk2[2 * slot + 1] = rhi;
+    w.stkm[slot] = (uint64_t)mhi << 32 | mlo;
+  }
+  uint32_t over;
+  sp += (int)rt_push_commit(B, sp, kStack2, &over);
+  wc.overflow += over;  // RT_EDEPTH, never silent
 }
 
 template <bool COUNT>
