@@ -22,6 +22,8 @@ static constexpr float kEps = 0.0000001f;  // cpu/hit.c:7 (float)1e-7
 // order, so LDS staging needs no s_barrier: only a compiler barrier that
 // keeps the LDS reads and writes in source order.
 __device__ __forceinline__ void wave_sync() { __asm__ volatile("" ::: "memory"); }
+// the compare's own scalar pair (__ballot goes through a select and a second compare)
+__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 __device__ __forceinline__ f3 ld3(const float* p) { return f3{p[0], p[1], p[2]}; }
 
@@ -176,10 +178,12 @@ __device__ __forceinline__ void consider_exact(const Ray& r, const float4& q0, c
 // (profiles/r04t_c5/pmc_sq.json: 2.13 G SALU to 3.89 G VALU per trace launch);
 // the v and t stages run for the whole wave once any lane passes u (a
 // divergent stage costs the wave the same VALU cycles anyway).  act: the
-// lane's query; the call itself must be wave-uniform.  (The plain divergent
-// `if (act) consider(...)` was the losing side of that measurement, removed.)
-__device__ __forceinline__ void consider_w(const Ray& r, bool act, const float4& q0, const float4& q1,
-                                           const float4& q2, Best& b) {
+// lane's query, am: the wave's mask of act (wave_ballot(act), taken once by
+// the caller, not per record); the call itself must be wave-uniform.  (The
+// plain divergent `if (act) consider(...)` was the losing side of that
+// measurement, removed.)
+__device__ __forceinline__ void consider_w(const Ray& r, bool act, uint64_t am, const float4& q0,
+                                           const float4& q1, const float4& q2, Best& b) {
   const float m = 1e-5f;  // as mt_candidate
   const f3 v0{q0.x, q0.y, q0.z}, e1{q0.w, q1.x, q1.y}, e2{q1.z, q1.w, q2.x};
   const f3 h = cross(r.d, e2);
@@ -187,8 +191,11 @@ __device__ __forceinline__ void consider_w(const Ray& r, bool act, const float4&
   const float rc = __builtin_amdgcn_rcpf(a);
   const f3 s = sub(r.o, v0);
   const float u = dot(s, h) * rc;
-  bool c = act && !(a > -kEps && a < kEps) && !(u < -1e-30f || u > 1.0f + m);
-  if (__ballot(c) == 0) return;
+  const bool ca = !(a > -kEps && a < kEps), cu0 = !(u < -1e-30f), cu1 = !(u > 1.0f + m);
+  bool c = act && ca && cu0 && cu1;
+  // the wave's verdict from the compares' own scalar pairs (one ballot each,
+  // ANDed in scalar registers: a ballot of c itself goes through a select)
+  if ((am & wave_ballot(ca) & wave_ballot(cu0) & wave_ballot(cu1)) == 0) return;
   const f3 q = cross(s, e1);
   const float v = dot(r.d, q) * rc;
   const float t = dot(e2, q) * rc;
@@ -200,8 +207,11 @@ __device__ __forceinline__ void consider_w(const Ray& r, bool act, const float4&
 // Converged call.  (The next record's reads issued during a test -- the
 // index clamped, no branch -- measured slower: trace 6.05 -> 6.51 ms on C5,
 // profiles/r05q_consider_w/ab_lds_pipe.log; round 1 found the same.)
-__device__ __forceinline__ void stage_test(const Ray& r, bool act, uint32_t n, Best& b, const float4* stage) {
-  for (uint32_t k = 0; k < n; k++) consider_w(r, act, stage[3 * k], stage[3 * k + 1], stage[3 * k + 2], b);
+__device__ __forceinline__ void stage_test(const Ray& r, bool act, uint64_t am, uint32_t n, Best& b,
+                                           const float4* stage) {
+  uint32_t k3 = 0;  // 3 k, kept in a VGPR: the record's LDS address advances there
+  __asm__ volatile("" : "+v"(k3));
+  for (uint32_t k = 0; k < n; k++, k3 += 3) consider_w(r, act, am, stage[k3], stage[k3 + 1], stage[k3 + 2], b);
 }
 
 // Any hit with new_dist > 0.01 (cpu/hit.c:93-109: collide_dist > 0 <=>

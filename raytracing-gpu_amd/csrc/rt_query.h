@@ -267,6 +267,7 @@ template <bool COUNT>
 __device__ __forceinline__ uint32_t cand_range(const KParams& p, const Ray& r, bool act, uint32_t s, uint32_t e,
                                                float bmax, Best& b, WaveCtx& w) {
   const int lane = w.lane;
+  const uint64_t am = wave_ballot(act);
   uint32_t tested = 0;
   for (uint32_t base = s; base < e; base += kOctRecs) {
     uint32_t prim = 0;
@@ -275,7 +276,7 @@ __device__ __forceinline__ uint32_t cand_range(const KParams& p, const Ray& r, b
       prim = p.cand[base + lane];
       keep = !(p.cand_skip[base + lane] > bmax);
     }
-    const uint64_t m = __ballot(keep);
+    const uint64_t m = wave_ballot(keep);
     if (m == 0) continue;
     const uint32_t n = (uint32_t)__popcll(m);
     const uint32_t slot = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -297,7 +298,7 @@ __device__ __forceinline__ uint32_t cand_range(const KParams& p, const Ray& r, b
     // do, measured slower here: C5 frame 15.96 -> 16.10 ms,
     // profiles/r03f_bench/ab.log; two per packed-float instruction, RT_CAND_PK
     // of round 3, slower too: profiles/r04e_pk/ab.log)
-    stage_test(r, act, n, b, w.stage);
+    stage_test(r, act, am, n, b, w.stage);
     tested += n;
   }
   return tested;

@@ -115,12 +115,16 @@ __device__ __forceinline__ void pop(Stack& s, uint32_t& i, float& t) {
 
 __device__ __forceinline__ f3 inv_dir(f3 d) { return f3{rt_inv(d.x), rt_inv(d.y), rt_inv(d.z)}; }
 
-// entry parameter of the eps-grown box, +inf on a miss (rt_cull.h)
+// slab test of the eps-grown box (rt_cull.h): the hit flag, t = entry parameter
+__device__ __forceinline__ bool box_hit(const Ray& r, f3 inv, float4 lo, float4 hi, float& t) {
+  return rt_box_hit(r.oh.x, r.oh.y, r.oh.z, r.ol.x, r.ol.y, r.ol.z, inv.x, inv.y, inv.z, lo.x,
+                    lo.y, lo.z, hi.x, hi.y, hi.z, &t);
+}
+
+// entry parameter of the eps-grown box, +inf on a miss
 __device__ __forceinline__ float box_enter(const Ray& r, f3 inv, float4 lo, float4 hi) {
   float t;
-  bool hit = rt_box_hit(r.oh.x, r.oh.y, r.oh.z, r.ol.x, r.ol.y, r.ol.z, inv.x, inv.y, inv.z, lo.x,
-                        lo.y, lo.z, hi.x, hi.y, hi.z, &t);
-  return hit ? t : __builtin_inff();
+  return box_hit(r, inv, lo, hi, t) ? t : __builtin_inff();
 }
 
 // Shadow walk box test (csrc/rt_shadow.hip): the box grown by mu eps instead

@@ -12,8 +12,6 @@
 namespace rt {
 
 __device__ __forceinline__ uint32_t uni(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
-// the compare's own scalar pair (__ballot goes through a select and a second compare)
-__device__ __forceinline__ uint64_t wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 // v_writelane_b32: `old` with lane `l` (wave-uniform) replaced by the wave-uniform x.  clang has
 // no builtin of that name; the declaration binds the LLVM intrinsic itself.
 __device__ int wave_writelane(int x, int l, int old) __asm("llvm.amdgcn.writelane");
@@ -56,6 +54,7 @@ __device__ __forceinline__ uint32_t wave_near_octant(bool act, f3 d, uint64_t am
 // workgroup must stay <= 10 KB for 16 workgroups per CU.
 static constexpr int kStageFlat = 192;
 static constexpr int kStageOct = 96;
+static constexpr int kStageKids = 16;  // of them, an interior node's <= 8 child boxes
 static constexpr int kStack2 = 96;  // wave stack entries (2 float4 each)
 // float4 slots of the stack area: the staged walk's kStack2 x (2 float4 + a
 // lane mask), or the per-lane stacks' kLdsStack x 64 x (index, t)
@@ -72,33 +71,38 @@ struct WaveCtx {
 
 // A fetch in flight: the wave's lanes hold float4 k, k+64, k+128 of src[0, n)
 // in registers (issued early so its latency overlaps other work), then commit
-// it to the LDS stage; n <= kStageFlat.
+// it to the LDS stage; n <= NMAX <= kStageFlat.  NMAX is the caller's bound on
+// n: the octree walks stage at most kStageOct float4, so their third slot
+// (l + 128 < n) can never be taken and is not compiled; the flat walks keep it.
 struct Fetch {
   float4 v0, v1, v2;
   int n;
 };
 
+template <int NMAX>
 __device__ __forceinline__ Fetch fetch_issue(const float4* __restrict__ src, int n, int l) {
+  static_assert(NMAX <= kStageFlat, "a fetch is at most three float4 per lane");
   Fetch f;
   f.n = n;
   if (l < n) f.v0 = src[l];
-  if (l + 64 < n) f.v1 = src[l + 64];
-  if (l + 128 < n) f.v2 = src[l + 128];
+  if (NMAX > 64 && l + 64 < n) f.v1 = src[l + 64];
+  if (NMAX > 128 && l + 128 < n) f.v2 = src[l + 128];
   return f;
 }
 
-
+template <int NMAX>
 __device__ __forceinline__ void fetch_commit(const Fetch& f, WaveCtx& w) {
   const int l = w.lane;
   wave_sync();  // after the previous readers of stage
   if (l < f.n) w.stage[l] = f.v0;
-  if (l + 64 < f.n) w.stage[l + 64] = f.v1;
-  if (l + 128 < f.n) w.stage[l + 128] = f.v2;
+  if (NMAX > 64 && l + 64 < f.n) w.stage[l + 64] = f.v1;
+  if (NMAX > 128 && l + 128 < f.n) w.stage[l + 128] = f.v2;
   wave_sync();
 }
 
+template <int NMAX>
 __device__ __forceinline__ void stage_load(const float4* __restrict__ src, int n, WaveCtx& w) {
-  fetch_commit(fetch_issue(src, n, w.lane), w);
+  fetch_commit<NMAX>(fetch_issue<NMAX>(src, n, w.lane), w);
 }
 
 template <int RECS>
@@ -117,12 +121,12 @@ __device__ void flat_closest_w(const KParams& p, const Ray& r, bool act, Best& b
                                WorkCount& wc) {
   if (__ballot(act) == 0) return;
   const uint32_t n = p.nrec;
-  Fetch f = fetch_issue(p.tri, 3 * (int)chunk<kFlatRecs>(n, 0), w.lane);
+  Fetch f = fetch_issue<kStageFlat>(p.tri, 3 * (int)chunk<kFlatRecs>(n, 0), w.lane);
   for (uint32_t base = 0; base < n; base += kFlatRecs) {
     uint32_t m = chunk<kFlatRecs>(n, base);
-    fetch_commit(f, w);
+    fetch_commit<kStageFlat>(f, w);
     uint32_t nb = base + kFlatRecs;
-    if (nb < n) f = fetch_issue(p.tri + 3 * (size_t)nb, 3 * (int)chunk<kFlatRecs>(n, nb), w.lane);
+    if (nb < n) f = fetch_issue<kStageFlat>(p.tri + 3 * (size_t)nb, 3 * (int)chunk<kFlatRecs>(n, nb), w.lane);
     // two records per step (mt_candidate2: two independent chains), the
     // survivors tested exactly in record order
     uint32_t k = 0;
@@ -151,12 +155,12 @@ __device__ bool flat_any_w(const KParams& p, const Ray& r, bool act, WaveCtx& w,
   uint32_t risk = 0;
   const uint32_t n = p.nrec;
   if (__ballot(alive) == 0 || n == 0) return false;
-  Fetch f = fetch_issue(p.tri, 3 * (int)chunk<kFlatRecs>(n, 0), w.lane);
+  Fetch f = fetch_issue<kStageFlat>(p.tri, 3 * (int)chunk<kFlatRecs>(n, 0), w.lane);
   for (uint32_t base = 0; base < n; base += kFlatRecs) {
     uint32_t m = chunk<kFlatRecs>(n, base);
-    fetch_commit(f, w);
+    fetch_commit<kStageFlat>(f, w);
     uint32_t nb = base + kFlatRecs;
-    if (nb < n) f = fetch_issue(p.tri + 3 * (size_t)nb, 3 * (int)chunk<kFlatRecs>(n, nb), w.lane);
+    if (nb < n) f = fetch_issue<kStageFlat>(p.tri + 3 * (size_t)nb, 3 * (int)chunk<kFlatRecs>(n, nb), w.lane);
     if (COUNT) {
       wc.tris += m;
       wc.sh_tris += m * (uint32_t)__popcll(__ballot(alive));
@@ -299,9 +303,18 @@ __device__ bool flat_any_tp(const KParams& p, const Ray& r, bool act, WorkCount&
 // takes is a function of the wave-uniform mask, dm and the children's
 // ballots alone (csrc/rt_push_plan.h), and the stack ends up byte for byte
 // what the serial loop left.
+// rt_box_wants (rt_cull.h) of every lane as the wave's mask: one ballot per
+// compare, ANDed in scalar registers.  (A ballot of the helper's own && is a
+// ballot of no compare: the compiler selects 0 / 1 into a VGPR and compares
+// that again, two VALU instructions per box.)
+__device__ __forceinline__ uint64_t box_wants_w(bool hit, float tmin, float dlen, float limit) {
+  return wave_ballot(hit) & wave_ballot(tmin != __builtin_inff()) & wave_ballot(rt_box_within(tmin, dlen, limit));
+}
+
+// wm: the lanes that want the node.
 template <bool ANY>
 __device__ __forceinline__ void stage_push_children(const Ray& r, f3 inv, uint32_t dm,
-                                                    uint32_t info, bool want, float limit,
+                                                    uint32_t info, uint64_t wm, float limit,
                                                     int& sp, WaveCtx& w, WorkCount& wc,
                                                     const float2* __restrict__ mu = nullptr) {
   const uint32_t mask = RT_NODE_MASK(info), cnt = RT_NODE_COUNT(info);
@@ -309,7 +322,6 @@ __device__ __forceinline__ void stage_push_children(const Ray& r, f3 inv, uint32
   // compares' own scalar pairs): the ballots never sit in scalar registers
   // past their own child's test
   int wlo = 0, whi = 0;
-  const uint64_t wm = wave_ballot(want);
 #pragma unroll
   for (int c = 0; c < 8; c++) {
     if ((uint32_t)c < cnt) {
@@ -319,8 +331,9 @@ __device__ __forceinline__ void stage_push_children(const Ray& r, f3 inv, uint32
         bc = wm & (mu ? wave_ballot(box_hit_sh(r, inv, clo, chi, mu[c]))  // exact-shadow mode's grown boxes
                       : wave_ballot(box_enter(r, inv, clo, chi) != __builtin_inff()));
       } else {
-        float t0 = box_enter(r, inv, clo, chi);
-        bc = wm & wave_ballot(t0 != __builtin_inff()) & wave_ballot(!(t0 * r.dlen > limit));
+        float t0;
+        const bool hit = box_hit(r, inv, clo, chi, t0);
+        bc = wm & box_wants_w(hit, t0, r.dlen, limit);
       }
       wlo = wave_writelane((int)(uint32_t)bc, c, wlo);
       whi = wave_writelane((int)(uint32_t)(bc >> 32), c, whi);
@@ -366,6 +379,7 @@ __device__ void staged_closest(const KParams& p, const Ray& r, bool act, Best& b
   if (w.lane == 0) w.stkm[0] = am;
   sp = 1;
   float limit = rt_prune_limit(b.dist, r.eps);
+  bool pruning = wave_ballot(b.dist != __builtin_inff()) != 0;  // some lane has a best
   while (sp > 0) {
     --sp;
     wave_sync();
@@ -375,33 +389,43 @@ __device__ void staged_closest(const KParams& p, const Ray& r, bool act, Best& b
     bool leaf = (info & RT_NODE_LEAF) != 0;
     uint32_t cnt = leaf ? RT_LEAF_COUNT(info) : RT_NODE_COUNT(info);
     // issue the node's payload fetch now; its latency overlaps the re-test
-    Fetch f = leaf ? fetch_issue(tri + 3 * (size_t)first, 3 * (int)chunk<kOctRecs>(cnt, 0), w.lane)
-                   : fetch_issue(node + 2 * (size_t)first, 2 * (int)cnt, w.lane);
-    // lanes that wanted it when pushed, re-tested against their best so far
+    Fetch f = leaf ? fetch_issue<kStageOct>(tri + 3 * (size_t)first, 3 * (int)chunk<kOctRecs>(cnt, 0), w.lane)
+                   : fetch_issue<kStageKids>(node + 2 * (size_t)first, 2 * (int)cnt, w.lane);
+    // Lanes that wanted it when pushed, re-tested against their best so far.
+    // Such a lane passed rt_box_wants on these very floats when the node was
+    // pushed, so its box is hit and the re-test is rt_box_within (rt_cull.h)
+    // alone: the exit parameter is not computed.  A lane without a best has
+    // limit = +inf and passes; the whole re-test is skipped while no lane has
+    // one.  (The root is pushed untested, and popped before any leaf.)
     bool want = ((lm >> w.lane) & 1) != 0;
-    if (want && b.dist != __builtin_inff()) {
-      float tn = box_enter(r, inv, lo, hi);
-      want = !(tn * r.dlen > limit);
+    uint64_t wm = wave_ballot(want);
+    if (pruning) {
+      float tn;
+      box_hit(r, inv, lo, hi, tn);
+      const bool within = rt_box_within(tn, r.dlen, limit);
+      want = want && within;
+      wm &= wave_ballot(within);
     }
-    if (__ballot(want) == 0) continue;
+    if (wm == 0) continue;
     if (COUNT) {
       wc.nodes++;
       wc.cl_nodes += (uint32_t)__popcll(__ballot(want));
     }
-    fetch_commit(f, w);
+    fetch_commit<kStageOct>(f, w);
     if (leaf) {
       for (uint32_t base = 0; base < cnt; base += kOctRecs) {
         uint32_t m = chunk<kOctRecs>(cnt, base);
-        if (base) stage_load(tri + 3 * (size_t)(first + base), 3 * (int)m, w);
-        stage_test(r, want, m, b, w.stage);
+        if (base) stage_load<kStageOct>(tri + 3 * (size_t)(first + base), 3 * (int)m, w);
+        stage_test(r, want, wm, m, b, w.stage);
       }
       limit = rt_prune_limit(b.dist, r.eps);
+      pruning = wave_ballot(b.dist != __builtin_inff()) != 0;
       if (COUNT) {
         wc.tris += cnt;
         wc.cl_tris += cnt * (uint32_t)__popcll(__ballot(want));
       }
     } else {
-      stage_push_children<false>(r, inv, dm, info, want, limit, sp, w, wc);
+      stage_push_children<false>(r, inv, dm, info, wm, limit, sp, w, wc);
     }
   }
 }
@@ -439,7 +463,7 @@ __device__ bool staged_any(const KParams& p, const Ray& r, bool act, WaveCtx& w,
       uint32_t cnt = RT_LEAF_COUNT(info);
       for (uint32_t base = 0; base < cnt && __ballot(want) != 0; base += kOctRecs) {
         uint32_t m = chunk<kOctRecs>(cnt, base);
-        stage_load(tri + 3 * (size_t)(first + base), 3 * (int)m, w);
+        stage_load<kStageOct>(tri + 3 * (size_t)(first + base), 3 * (int)m, w);
         if (COUNT) wc.tris += m;
         for (uint32_t k = 0; k < m; k++) {
           if (COUNT) wc.sh_tris += (uint32_t)__popcll(__ballot(want));
@@ -454,8 +478,8 @@ __device__ bool staged_any(const KParams& p, const Ray& r, bool act, WaveCtx& w,
       }
       if (__ballot(alive) == 0) break;
     } else {
-      stage_load(node + 2 * (size_t)first, 2 * (int)RT_NODE_COUNT(info), w);
-      stage_push_children<true>(r, inv, dm, info, want, 0.0f, sp, w, wc,
+      stage_load<kStageOct>(node + 2 * (size_t)first, 2 * (int)RT_NODE_COUNT(info), w);
+      stage_push_children<true>(r, inv, dm, info, wave_ballot(want), 0.0f, sp, w, wc,
                                 p.node_mu ? p.node_mu + first : nullptr);
     }
   }

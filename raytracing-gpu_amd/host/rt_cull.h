@@ -83,6 +83,32 @@ RT_CULL_FN int rt_box_hit(float ohx, float ohy, float ohz, float olx, float oly,
   return tmax >= fmaxf(tmin, 0.0f);
 }
 
+/* The closest-hit packet walk's verdicts on a box, straight from rt_box_hit's
+ * flag and entry parameter (tests/native/box_verdict.cpp compares both with
+ * the formulas they replace over every kind of float input).
+ *
+ * rt_box_within: the box's entry distance does not exceed the prune limit.
+ * This alone is the re-test of a popped node by a lane that wanted it when it
+ * was pushed: that lane's slab test of the same floats hit, and for a hit
+ *   t0 = hit ? tmin : +inf;  !(t0 * dlen > limit)
+ * is this compare.
+ *
+ * rt_box_wants: the lane wants the box at the push.  Decides as
+ *   t0 = hit ? tmin : +inf;  t0 != +inf && !(t0 * dlen > limit)
+ * for every float input, without the select that folded a miss into +inf.
+ * The tmin != +inf compare stays: a hit with tmin = +inf (a slab whose planes
+ * both overflow, tmax = +inf) under limit = +inf is refused by the formula
+ * above and would pass without it. */
+RT_CULL_FN int rt_box_within(float tmin, float dlen, float limit)
+{
+  return !(tmin * dlen > limit);
+}
+
+RT_CULL_FN int rt_box_wants(int hit, float tmin, float dlen, float limit)
+{
+  return hit && tmin != __builtin_inff() && rt_box_within(tmin, dlen, limit);
+}
+
 /* A node whose entry parameter t_enter satisfies t_enter * |d| > limit cannot
  * hold a triangle whose new_dist is <= best (limit = +inf without a best). */
 RT_CULL_FN float rt_prune_limit(float best, float eps)
