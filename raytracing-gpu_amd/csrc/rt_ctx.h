@@ -95,6 +95,10 @@ struct rt_hip_ctx {
   DevBuf<float> d_nrm;
   DevBuf<float> d_mat;
   DevBuf<float> d_light;
+  // the shading tables derived from d_mat and d_light (csrc/rt_shade_rows.h;
+  // rt_hip.cpp shade_tables, after every upload of either)
+  DevBuf<float> d_mshade;
+  DevBuf<float> d_lshade;
   DevBuf<float4> d_node;
   DevBuf<uint32_t> d_counter;
   unsigned long long* d_stats = nullptr;  // view: into d_counter, past the item counters
@@ -277,6 +281,8 @@ static inline KParams scene_params(const rt_hip_ctx* c) {
   p.nrm = c->d_nrm;
   p.mat = c->d_mat;
   p.light = c->d_light;
+  p.mshade = c->d_mshade;
+  p.lshade = c->d_lshade;
   p.node = c->d_node;
   p.nrec = c->nrec;
   p.nlight = c->nlight;

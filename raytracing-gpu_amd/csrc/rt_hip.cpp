@@ -37,6 +37,20 @@ static int upload(DevBuf<T>& dst, const void* src, size_t bytes) {
   return RT_OK;
 }
 
+// The shading tables (csrc/rt_shade_rows.h) of the light rows in d_light
+// (lights) and / or the material rows in d_mat (materials), after an upload of
+// either: allocated to the rows' count and derived on the device, finished
+// when this returns (setup; a render may run on any stream).
+static int shade_tables(rt_hip_ctx* c, bool lights, bool materials) {
+  const uint32_t nl = lights ? c->nlight : 0u;
+  const uint32_t no = materials ? (uint32_t)(c->mat_host.size() / RT_MAT_FLOATS) : 0u;
+  if (lights) HIP_TRY(c->d_lshade.alloc((size_t)nl * RT_LSHADE_FLOATS_D));
+  if (materials) HIP_TRY(c->d_mshade.alloc((size_t)no * RT_MAT_FLOATS));
+  HIP_TRY(rt_launch_shade_tables(c->d_light, nl, c->d_lshade, c->d_mat, no, c->d_mshade, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
 extern "C" void rt_hip_destroy(rt_hip_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -329,6 +343,7 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
   c->info.build_seconds = std::chrono::duration<double>(dev_build ? t2 - t0 : t1 - t0).count();
   if (fs.mat) c->mat_host.assign(fs.mat, fs.mat + fs.nobj * RT_MAT_FLOATS);
   rt_flat_free(&fs);
+  if (!rc) rc = shade_tables(c, true, true);
   if (rc) {
     rt_hip_destroy(c);
     return rc;
@@ -994,6 +1009,9 @@ extern "C" int rt_hip_set_lights(rt_hip_ctx* c, const rt_light* lights, size_t n
   // the last render's parameters are views into the context's buffers
   c->last_p.light = c->d_light;
   c->last_p.nlight = c->nlight;
+  rc = shade_tables(c, true, false);
+  c->last_p.lshade = c->d_lshade;
+  if (rc) return rc;
   if (!(c->light_buffers && c->accel == RT_ACCEL_OCTREE && c->d_node)) return RT_OK;  // no light has a buffer
   const bool current = c->d_lbuf && c->lb_ulps == c->eps_ulps && c->lb_proven == c->exact_shadows &&
                        c->lb_dev.size() == old_n && c->lb_host.size() == old_n && c->lb_failed.size() == old_n;
@@ -1061,7 +1079,9 @@ extern "C" int rt_hip_set_materials(rt_hip_ctx* c, const rt_object* objects, siz
   if (rc) return rc;
   HIP_TRY(hipMemcpy(c->d_mat, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
   c->mat_host = rows;
-  return RT_OK;
+  const int tables = shade_tables(c, false, true);
+  c->last_p.mshade = c->d_mshade;  // (the last render's parameters are views into the context's buffers)
+  return tables;
 }
 
 extern "C" int rt_hip_set_keep_visibility(rt_hip_ctx* c, int enable) {
@@ -1095,6 +1115,8 @@ extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
     p.light = sp.light;
     p.nlight = sp.nlight;
     p.mat = sp.mat;
+    p.mshade = sp.mshade;
+    p.lshade = sp.lshade;
     p.eps_rel = sp.eps_rel;
     p.eps_rel_cam = sp.eps_rel_cam;
   }
@@ -1123,7 +1145,8 @@ extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
   // would fault the card, not fail the call)
   if (!p.tri_prim && (p.lbuf || p.n_sh_global)) return rt_set_error(RT_EHIP, "relight: prim-order records missing");
   if (!p.hit || !p.hit_prev || !p.hit_term || !p.hit_lit || !p.hit_count || !p.shade_counter || !p.stats ||
-      !p.last || !p.out || (p.nlight && !p.light) || (p.nrec && (!p.tri || !p.nrm)) || !p.mat ||
+      !p.last || !p.out || (p.nlight && (!p.light || !p.lshade)) || (p.nrec && (!p.tri || !p.nrm)) || !p.mat ||
+      !p.mshade ||
       p.hit_cap != c->hit_cap() || !c->d_hit_lit.holds((size_t)p.hit_cap * RT_HIT_REGIONS))
     return rt_set_error(RT_EHIP, "relight: device buffers missing");
   HIP_TRY(rt_launch_relight_zero(&p, s));

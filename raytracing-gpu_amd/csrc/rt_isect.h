@@ -51,17 +51,25 @@ struct Ray {
   f3 oh, ol;   // o + eps, o - eps: the grown slab planes' offsets (rt_cull.h)
 };
 
-__device__ __forceinline__ Ray make_ray(const KParams& p, f3 o, f3 d, float eps_rel) {
+// dlen = length(d), computed by the caller or taken from where it was
+// computed before (a directional light's row, rt_shade_rows.h)
+__device__ __forceinline__ Ray make_ray_len(const KParams& p, f3 o, f3 d, float dlen, float eps_rel) {
   Ray r;
   r.o = o;
   r.d = d;
-  r.dlen = length(d);
+  r.dlen = dlen;
   r.eps = rt_cull_eps(eps_rel, o.x - p.scene_c.x, o.y - p.scene_c.y, o.z - p.scene_c.z,
                       p.scene_cmag, p.scene_r);
   r.oh = f3{o.x + r.eps, o.y + r.eps, o.z + r.eps};
   r.ol = f3{o.x - r.eps, o.y - r.eps, o.z - r.eps};
   return r;
 }
+__device__ __forceinline__ Ray make_ray(const KParams& p, f3 o, f3 d, float eps_rel) {
+  return make_ray_len(p, o, d, length(d), eps_rel);
+}
+
+// normalize(d) as the hit point takes it: the three IEEE quotients d / |d|
+__device__ __forceinline__ f3 unit_dir(const Ray& r) { return f3{r.d.x / r.dlen, r.d.y / r.dlen, r.d.z / r.dlen}; }
 
 // The hit point o + normalize(d) * (t*|d|) (cpu/hit.c:35-37,58), with
 // normalize(d) recomputed here (the same IEEE divisions every time, so the
@@ -74,6 +82,11 @@ __device__ __forceinline__ f3 hit_point(const Ray& r, float t) {
 // new_dist = |hit point - o| (cpu/hit.c:58)
 __device__ __forceinline__ float hit_dist(const Ray& r, float t) {
   return length(sub(hit_point(r, t), r.o));
+}
+// the same with nd = unit_dir(r) from the caller (the light buffers' scan: a
+// directional light's is a constant of the light)
+__device__ __forceinline__ float hit_dist(const Ray& r, f3 nd, float t) {
+  return length(sub(add(r.o, scale(nd, t * r.dlen)), r.o));
 }
 
 // Conservative pre-filter of the Moller-Trumbore test.  h, a, s.h, d.q, e2.q
@@ -220,25 +233,35 @@ __device__ __forceinline__ void stage_test(const Ray& r, bool act, uint64_t am, 
 // host/accel.c): its closest hit then counts in collide_dist whatever
 // triangle the walk met first.  A hit on a flagged object sets `risk`
 // (reported as RT_EZERONORMAL, never silent).
-__device__ __forceinline__ bool any_hit_exact(const Ray& r, const float4& q0, const float4& q1,
+__device__ __forceinline__ bool any_hit_exact(const Ray& r, f3 nd, const float4& q0, const float4& q1,
                                               const float4& q2, uint32_t& risk);
 
-__device__ __forceinline__ bool any_hit_rec(const Ray& r, const float4& q0, const float4& q1,
+// nd = unit_dir(r), from the caller: the light buffers' scan has a directional
+// light's from the light's row (rt_shade_rows.h)
+__device__ __forceinline__ bool any_hit_rec(const Ray& r, f3 nd, const float4& q0, const float4& q1,
                                             const float4& q2, uint32_t& risk) {
   f3 v0{q0.x, q0.y, q0.z}, e1{q0.w, q1.x, q1.y}, e2{q1.z, q1.w, q2.x};
   if (!mt_candidate(r.o, r.d, v0, e1, e2, __builtin_inff())) return false;
-  return any_hit_exact(r, q0, q1, q2, risk);
+  return any_hit_exact(r, nd, q0, q1, q2, risk);
+}
+__device__ __forceinline__ bool any_hit_rec(const Ray& r, const float4& q0, const float4& q1,
+                                            const float4& q2, uint32_t& risk) {
+  return any_hit_rec(r, unit_dir(r), q0, q1, q2, risk);
 }
 
 // the exact test of a prefilter survivor (any_hit_rec)
-__device__ __forceinline__ bool any_hit_exact(const Ray& r, const float4& q0, const float4& q1,
+__device__ __forceinline__ bool any_hit_exact(const Ray& r, f3 nd, const float4& q0, const float4& q1,
                                               const float4& q2, uint32_t& risk) {
   f3 v0{q0.x, q0.y, q0.z}, e1{q0.w, q1.x, q1.y}, e2{q1.z, q1.w, q2.x};
   float t, u, v;
   if (!mt_test(r.o, r.d, v0, e1, e2, t, u, v)) return false;
-  if (!((double)hit_dist(r, t) > 0.01)) return false;
+  if (!((double)hit_dist(r, nd, t) > 0.01)) return false;
   risk |= __float_as_uint(q2.w) & RT_REC_ZERO_RISK;
   return true;
+}
+__device__ __forceinline__ bool any_hit_exact(const Ray& r, const float4& q0, const float4& q1,
+                                              const float4& q2, uint32_t& risk) {
+  return any_hit_exact(r, unit_dir(r), q0, q1, q2, risk);
 }
 
 }  // namespace rt

@@ -13,6 +13,9 @@
 #define RT_ACCEL_OCTREE_D 1
 #define RT_MAT_FLOATS_D 12
 #define RT_LIGHT_FLOATS_D 8
+// one row of the light shading table (KParams::lshade, csrc/rt_shade_rows.h):
+// four float4, so a wave-uniform row is one 64-byte scalar load
+#define RT_LSHADE_FLOATS_D 16
 // closest-hit queries one path may make before the render reports RT_EDEPTH:
 // cpu/rt recurses while coef >= 0.01 (cpu/raytracer.c:19-34), which is
 // unbounded for mirrors of Nr >= 1; paths of Nr < 1 end long before this
@@ -194,6 +197,13 @@ struct KParams {
   // lights 0..31 whose shadow queries run; the others' outcomes are the bits
   // of the record's stored mask hit_lit (csrc/rt_relight.h).  Appended too
   uint32_t relight_dirty;
+  // shading tables (csrc/rt_shade_rows.h), derived on the device from mat and
+  // light wherever those are uploaded: the constants of a material
+  // (RT_MAT_FLOATS_D per object, as mat) and of a light (RT_LSHADE_FLOATS_D per
+  // light) that the shade pass would otherwise compute again per record.  The
+  // trace, the probes and the compatibility mode read mat and light.  Appended
+  const float* mshade;
+  const float* lshade;
 };
 // (the bits of frame_check[0], RT_FRAME_*: rt_counters.h)
 
@@ -218,6 +228,10 @@ extern "C" hipError_t rt_launch_fold(const KParams* p, hipStream_t stream);
 extern "C" hipError_t rt_launch_relight_zero(const KParams* p, hipStream_t stream);
 extern "C" hipError_t rt_launch_recolour(const KParams* p, int cus, hipStream_t stream);
 extern "C" hipError_t rt_launch_reshade(const KParams* p, int accel, int policy, int grid, hipStream_t stream);
+// The shading tables of `nlight` light rows and `nobj` material rows (either
+// count may be 0: that table is left alone)
+extern "C" hipError_t rt_launch_shade_tables(const float* light, uint32_t nlight, float* lshade, const float* mat,
+                                             uint32_t nobj, float* mshade, hipStream_t stream);
 // shadow-query probe: light li's shadow ray from each of n origins through
 // the light buffer p->lbuf[li] (brute = 0) or brute force over nprim
 // prim-order records p->tri_prim (brute = 1); out[i] = shadowed

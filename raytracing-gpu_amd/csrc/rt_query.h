@@ -9,6 +9,7 @@
 #pragma once
 
 #include "rt_lightbuf_cell.h"
+#include "rt_shade_rows.h"
 #include "rt_walk_lane.h"
 #include "rt_walk_wave.h"
 
@@ -125,8 +126,10 @@ __device__ __forceinline__ LbRange lbuf_range(const RtLightBuf& L, const Ray& r)
 // instead of 8 -- C5 shade 1.96 -> 1.85 ms (profiles/r07_shade/; at 8 waves
 // it spills: 1.92; at 6: 1.93).  Round 3 measured the lookahead at 8 waves
 // only (spills, 2.72 ms).  (The loop without the lookahead was removed.)
+// nd = unit_dir(r) (a directional light's: its row's).
 template <bool COUNT>
-__device__ bool lbuf_scan(const KParams& p, const RtLightBuf& L, const Ray& r, const LbRange& g, LaneCount& lc) {
+__device__ bool lbuf_scan(const KParams& p, const RtLightBuf& L, const Ray& r, f3 nd, const LbRange& g,
+                          LaneCount& lc) {
   for (int h = 0; h < 2; h++) {
     const float q = h == 0 ? g.lim : __builtin_inff();
     // the next entry's record in flight while this one is tested
@@ -152,7 +155,7 @@ __device__ bool lbuf_scan(const KParams& p, const RtLightBuf& L, const Ray& r, c
         lc.tris += lanes_distinct(k);
         lc.ltris++;
       }
-      if (any_hit_rec(r, a0, a1, a2, lc.risk)) return true;
+      if (any_hit_rec(r, nd, a0, a1, a2, lc.risk)) return true;
     }
   }
   for (uint32_t k = 0; k < L.nglobal; k++) {
@@ -161,14 +164,29 @@ __device__ bool lbuf_scan(const KParams& p, const RtLightBuf& L, const Ray& r, c
       lc.tris += lanes_distinct(L.global[k]);
       lc.ltris++;
     }
-    if (any_hit_rec(r, t[0], t[1], t[2], lc.risk)) return true;
+    if (any_hit_rec(r, nd, t[0], t[1], t[2], lc.risk)) return true;
   }
   return false;
 }
 
 template <bool COUNT>
 __device__ bool lbuf_any(const KParams& p, const RtLightBuf& L, const Ray& r, LaneCount& lc) {
-  return lbuf_scan<COUNT>(p, L, r, lbuf_range(L, r), lc);
+  return lbuf_scan<COUNT>(p, L, r, unit_dir(r), lbuf_range(L, r), lc);
+}
+
+// The shadow ray (o, d) of light li and its unit direction.  A directional
+// light's d is scale(v, -1) whatever the origin, so |d| and d / |d| come from
+// the light's row (rt_shade_rows.h: the same operations, done once); a point
+// light's are computed here.  li wave-uniform.
+__device__ __forceinline__ Ray lbuf_ray(const KParams& p, f3 o, f3 d, uint32_t type, uint32_t li, f3& nd) {
+  if (type == 1) {
+    const LightShade S = LightRowsUniform{p.lshade}[li];
+    nd = S.nd;
+    return make_ray_len(p, o, d, S.dlen, p.eps_rel);
+  }
+  const Ray r = make_ray(p, o, d, p.eps_rel);
+  nd = unit_dir(r);
+  return r;
 }
 
 // Shadow query (collide_dist > 0.01, cpu/light.c:24-31) of a light of the
@@ -179,13 +197,16 @@ __device__ __forceinline__ bool shadow_q(const KParams& p, f3 o, f3 d, uint32_t 
                                          const LbRange* pre = nullptr, bool can_defer = true) {
   uint64_t am = __ballot(act);
   wc.shadow += (uint32_t)__popcll(am);
-  Ray r = make_ray(p, o, d, p.eps_rel);
-  if (ACCEL == RT_ACCEL_FLAT_D)
+  if (ACCEL == RT_ACCEL_FLAT_D) {
+    const Ray r = make_ray(p, o, d, p.eps_rel);
     return use_tp(p, act) ? flat_any_tp<COUNT>(p, r, act, wc) : flat_any_w<COUNT>(p, r, act, w, wc);
+  }
   if (POL == RT_POLICY_LBUF) {  // every such light has a buffer (rt_hip.cpp): no walk, no global prims
-    const RtLightBuf& L = p.lbuf[li];
+    const RtLightBuf L = lbuf_desc(p.lbuf, li);
+    f3 nd;
+    const Ray r = lbuf_ray(p, o, d, type, li, nd);
     LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool hit = act && (pre ? lbuf_scan<COUNT>(p, L, r, *pre, lc) : lbuf_any<COUNT>(p, L, r, lc));
+    bool hit = act && lbuf_scan<COUNT>(p, L, r, nd, pre ? *pre : lbuf_range(L, r), lc);
     absorb<COUNT>(wc, lc, true);
     if (L.proven) {  // as below
       const bool out = act && !(o.x >= L.olo[0] && o.x <= L.ohi[0] && o.y >= L.olo[1] && o.y <= L.ohi[1] &&
@@ -202,13 +223,17 @@ __device__ __forceinline__ bool shadow_q(const KParams& p, f3 o, f3 d, uint32_t 
   bool staged = POL == RT_POLICY_STAGED ||
                 (POL == RT_POLICY_DIR_STAGED && type == 1 && __popcll(am) >= kPacketMin);
   bool hit, walked = true;
+  f3 nd;
+  const Ray r = lbuf_ray(p, o, d, type, li, nd);
   if (staged) {
     hit = staged_any<COUNT>(p, r, act, w, wc);
   } else if (p.lbuf && p.lbuf[li].kind != RT_LB_NONE) {
     walked = false;
+    // (the descriptor by reference, through the vector cache: by value in
+    // SGPRs, this kernel, which keeps the walk's state too, spilled more)
     const RtLightBuf& L = p.lbuf[li];
     LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
-    hit = act && (pre ? lbuf_scan<COUNT>(p, L, r, *pre, lc) : lbuf_any<COUNT>(p, L, r, lc));
+    hit = act && lbuf_scan<COUNT>(p, L, r, nd, pre ? *pre : lbuf_range(L, r), lc);
     absorb<COUNT>(wc, lc, true);
     if (L.proven) {
       // the proof assumed origins in its box; the rare others (hit points of

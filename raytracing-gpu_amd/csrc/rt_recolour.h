@@ -40,19 +40,20 @@ __global__ __launch_bounds__(256) void relight_zero_kernel(KParams p) {
   if (t < RT_STAT_SETS * RT_STAT_STRIDE && shade_stat_slot(t % RT_STAT_STRIDE)) p.stats[t] = 0ull;
 }
 
-// lights a workgroup stages in LDS (8 floats each); a longer table is read
-// through the vector cache instead
+// lights a workgroup stages in LDS (their shading rows, RT_LSHADE_FLOATS_D
+// floats each); a longer table is read from global memory instead
 static constexpr uint32_t kRecolourLights = 64;
 
 // A record's local colour under `nlight` lights from its stored mask (lights
 // 0..31; a casting light from index 32 up has no bit and the host never takes
 // this path with one): shade_record's blocks of 32 in the same order.
-__device__ __forceinline__ col recolour_sum(const float* light, uint32_t nlight, uint32_t mask, const float* m,
+template <class Rows>
+__device__ __forceinline__ col recolour_sum(const Rows& rows, uint32_t nlight, uint32_t mask, const float* ms,
                                             f3 P, f3 N) {
   col acc = init_color(0.0f, 0.0f, 0.0f);
   for (uint32_t l0 = 0; l0 < nlight; l0 += 32) {
     const uint32_t l1 = nlight - l0 < 32u ? nlight : l0 + 32u;
-    acc = lights_sum(light, acc, l0, l1, l0 == 0 ? mask : 0u, m, P, N);
+    acc = lights_sum(rows, acc, l0, l1, l0 == 0 ? mask : 0u, ms, P, N);
   }
   return acc;
 }
@@ -65,10 +66,11 @@ __device__ __forceinline__ col recolour_sum(const float* light, uint32_t nlight,
 // row (10 floats of 48 B, gathered by object) comes through the vector cache.
 template <int K = 0>
 __global__ __launch_bounds__(256) void recolour_kernel(KParams p) {
-  __shared__ float s_light[kRecolourLights * RT_LIGHT_FLOATS_D];
+  __shared__ float4 s_light[kRecolourLights * RT_LSHADE_FLOATS_D / 4];
   const bool staged = p.nlight <= kRecolourLights;
   if (staged)
-    for (uint32_t i = threadIdx.x; i < p.nlight * RT_LIGHT_FLOATS_D; i += blockDim.x) s_light[i] = p.light[i];
+    for (uint32_t i = threadIdx.x; i < p.nlight * (RT_LSHADE_FLOATS_D / 4); i += blockDim.x)
+      s_light[i] = ((const float4*)p.lshade)[i];
   __syncthreads();
   uint32_t end[RT_HIT_REGIONS];  // exclusive ends of the regions in the flattened order (wave-uniform)
   uint32_t total = 0;
@@ -93,9 +95,9 @@ __global__ __launch_bounds__(256) void recolour_kernel(KParams p) {
     const float4 r0 = p.hit[2 * a], r1 = p.hit[2 * a + 1];
     const uint32_t mask = p.hit_lit[a];
     const f3 P{r0.x, r0.y, r0.z}, N{r0.w, r1.x, r1.y};
-    const float* m = p.mat + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
-    const col local = staged ? recolour_sum(s_light, p.nlight, mask, m, P, N)
-                             : recolour_sum(p.light, p.nlight, mask, m, P, N);
+    const float* ms = p.mshade + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
+    const col local = staged ? recolour_sum(LightRowsMem{s_light}, p.nlight, mask, ms, P, N)
+                             : recolour_sum(LightRowsUniform{p.lshade}, p.nlight, mask, ms, P, N);
     const col tm = color_mul(local, r1.z);  // coef
     p.hit_term[a] = make_float4(tm.r, tm.g, tm.b, 0.0f);
   }

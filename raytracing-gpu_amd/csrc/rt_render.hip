@@ -356,12 +356,12 @@ __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t
         P = f3{r0.x, r0.y, r0.z};
       }
       for (uint32_t li = l0; li < l1; li++) {
-        const float* L = p.light + RT_LIGHT_FLOATS_D * li;
-        const uint32_t type = __float_as_uint(L[0]);
+        const LightShade L = LightRowsUniform{p.lshade}[li];
+        const uint32_t type = L.type;
         if (type != 1 && type != 2) continue;
         if constexpr (RELIGHT)
           if (l0 == 0 && !((p.relight_dirty >> li) & 1u)) continue;  // clean: no query (wave-uniform)
-        const f3 lv = f3{L[4], L[5], L[6]};
+        const f3 lv = L.v;
         const uint64_t c0 = COUNT ? __builtin_readcyclecounter() : 0ull;
         bool df = false;
         // (issuing the first two lights' cell-range loads before either
@@ -391,8 +391,8 @@ __device__ __forceinline__ col shade_record(const KParams& p, bool valid, size_t
     if (!valid) continue;
     const float4 r0 = p.hit[2 * a], r1 = p.hit[2 * a + 1];
     const f3 P{r0.x, r0.y, r0.z}, N{r0.w, r1.x, r1.y};
-    const float* m = p.mat + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
-    acc = lights_sum(p.light, acc, l0, l1, lit, m, P, N);
+    const float* ms = p.mshade + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
+    acc = lights_sum(LightRowsUniform{p.lshade}, acc, l0, l1, lit, ms, P, N);
   }
   return acc;
 }
@@ -498,9 +498,8 @@ __global__ __launch_bounds__(256) void oob_fix_kernel(KParams p, uint32_t nprim)
     uint32_t mine = 0, risk = 0;
     for (uint32_t li = 0; li < 32 && li < p.nlight; li++) {
       if (!((q.y >> li) & 1u)) continue;
-      const float* L = p.light + RT_LIGHT_FLOATS_D * li;
-      const uint32_t type = __float_as_uint(L[0]);
-      const Ray r = make_ray(p, P, shadow_dir(type, f3{L[4], L[5], L[6]}, P), p.eps_rel);
+      const LightShade L = LightRowsUniform{p.lshade}[li];  // (li is the workgroup's)
+      const Ray r = make_ray(p, P, shadow_dir(L.type, L.v, P), p.eps_rel);
       bool h = false;
       const uint32_t end = min(nprim, (c + 1) * kFixChunk);
       for (uint32_t k = c * kFixChunk + threadIdx.x; k < end && !h; k += blockDim.x) {
@@ -540,9 +539,8 @@ __global__ __launch_bounds__(256) void oob_fix_batch_kernel(KParams p, uint32_t 
       const f3 P{r0.x, r0.y, r0.z};
       for (uint32_t li = 0; li < 32 && li < p.nlight; li++) {
         if (!((q.y >> li) & 1u) || m >= kFixBatch) continue;
-        const float* L = p.light + RT_LIGHT_FLOATS_D * li;
-        const uint32_t type = __float_as_uint(L[0]);
-        qs[m].r = make_ray(p, P, shadow_dir(type, f3{L[4], L[5], L[6]}, P), p.eps_rel);
+        const LightShade L = LightRowsUniform{p.lshade}[li];
+        qs[m].r = make_ray(p, P, shadow_dir(L.type, L.v, P), p.eps_rel);
         qs[m].e = e;
         qs[m].li = li;
         m++;
@@ -574,9 +572,9 @@ __global__ __launch_bounds__(64) void oob_reshade_kernel(KParams p) {
     const uint32_t lit0 = q.z | (q.y & ~q.w);
     const float4 r0 = p.hit[2 * a], r1 = p.hit[2 * a + 1];
     const f3 P{r0.x, r0.y, r0.z}, N{r0.w, r1.x, r1.y};
-    const float* m = p.mat + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
-    const col acc =
-        lights_sum(p.light, init_color(0.0f, 0.0f, 0.0f), 0, p.nlight < 32u ? p.nlight : 32u, lit0, m, P, N);
+    const float* ms = p.mshade + RT_MAT_FLOATS_D * (size_t)__float_as_uint(r1.w);
+    const col acc = lights_sum(LightRowsUniform{p.lshade}, init_color(0.0f, 0.0f, 0.0f), 0,
+                               p.nlight < 32u ? p.nlight : 32u, lit0, ms, P, N);
     const col tm = color_mul(acc, r1.z);  // coef
     p.hit_term[a] = make_float4(tm.r, tm.g, tm.b, 0.0f);
     if (p.hit_lit) p.hit_lit[a] = lit0;
@@ -747,6 +745,7 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
 }  // namespace rt
 
 #include "rt_recolour.h"  // relight_zero_kernel, recolour_kernel: after every render kernel
+#include "rt_shade_tables.h"  // shade_tables_kernel: after those
 
 // ---------------------------------------------------------------- launchers
 // One instantiation per (kernel, accel, work counting, policy); the default
@@ -931,4 +930,14 @@ extern "C" hipError_t rt_launch_reshade(const KParams* p, int accel, int policy,
                       ? (const void*)shade_kernel<RT_ACCEL_OCTREE_D, false, RT_POLICY_LBUF, true>
                       : (const void*)shade_kernel<RT_ACCEL_OCTREE_D, false, RT_POLICY_DEFAULT, true>;
   return launch_kernel(k, grid, p, stream);
+}
+
+// The shading tables (rt_shade_tables.h): one thread per light or material row.
+extern "C" hipError_t rt_launch_shade_tables(const float* light, uint32_t nlight, float* lshade, const float* mat,
+                                             uint32_t nobj, float* mshade, hipStream_t stream) {
+  const uint32_t n = nlight > nobj ? nlight : nobj;
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL((rt::shade_tables_kernel<0>), dim3((n + 255) / 256), dim3(256), 0, stream, light, nlight, lshade,
+                     mat, nobj, mshade);
+  return hipGetLastError();
 }
