@@ -171,6 +171,20 @@ size_t rt_hip_tile_buffer_floats(int width, int height, int nranks);
  * (a hipStream_t; NULL = the context's stream). */
 int rt_hip_render(rt_hip_ctx *ctx, const rt_frame *frame, int rank, int nranks, float *d_tiles,
                   void *stream);
+/* A caller that streams frames (enqueues the next rt_hip_render while the
+ * last one runs) gets the next frame's candidate lists built on a second
+ * stream of the context, beside the last frame's shade pass: the build waits
+ * for that frame's trace kernel by an event, and `stream` waits for the
+ * build before the trace, so every call stays ordered on `stream` as before
+ * (default 1; the first frame of a size, a frame whose buffers grow, consumed
+ * lists and rt_hip_render_compat build on `stream`).  Images and counters
+ * are the same either way.  0 turns it off (A/B runs).  With it on, a timed
+ * frame's list span and render span (include/rt_hip_test.h
+ * rt_hip_frame_times) overlap the previous frame's and no longer add up to
+ * the frame.  rt_hip_overlap_builds: the context's builds that ran on the
+ * second stream so far. */
+int rt_hip_set_overlap_lists(rt_hip_ctx *ctx, int enable);
+int rt_hip_overlap_builds(const rt_hip_ctx *ctx, unsigned long long *n);
 /* Waits for the last render and returns its counters.  The counters are
  * filled in whatever the return code: RT_EHITBUF (render again),
  * RT_EDEPTH / RT_EZERONORMAL (the image may differ from cpu/rt's there),

@@ -67,7 +67,11 @@ int rt_hip_set_camera_slack(rt_hip_ctx *ctx, float ulps);
  * stream before the camera candidate lists, before and after each of its
  * three kernels (a ring of the last 1024 frames; enabling clears it).
  * rt_hip_frame_times waits for the last n timed frames and returns their two
- * spans in milliseconds, oldest first (lists_ms ~0 without lists). */
+ * spans in milliseconds, oldest first (lists_ms ~0 without lists).  A list
+ * build that ran on the context's second stream (rt_hip.h
+ * rt_hip_set_overlap_lists) is timed there, from its own start to its own
+ * end beside the previous frame's shade pass: lists_ms + render_ms is then
+ * more than the frame took. */
 int rt_hip_set_timing(rt_hip_ctx *ctx, int enable);
 int rt_hip_frame_times(rt_hip_ctx *ctx, int n, float *lists_ms, float *render_ms);
 /* The render span of the same frames split by kernel: trace (closest-hit

@@ -29,6 +29,7 @@
 #include "rt_cand.h"
 #include "rt_kernels.h"
 #include "rt_forecast.h"
+#include "rt_overlap.h"
 #include "rt_lightbuf.h"
 #include "rt_mem.h"
 #include "rt_relight.h"
@@ -90,6 +91,14 @@ struct rt_hip_ctx {
   int count_work = 0;
   int grid = 0;
   StreamOwner stream;
+  // the next frame's list build beside the previous frame's shade pass
+  // (csrc/rt_overlap.h): the side stream, the end of the last trace that read
+  // the list buffers, the end of the side stream's build
+  StreamOwner side_stream;
+  hipEvent_t ev_lists_free = nullptr, ev_lists_done = nullptr;
+  ListOverlap overlap;
+  DevBuf<uint32_t> d_list_flag;  // 2 words: an asynchronous build's overflow flag, alternated per build
+  const uint32_t* list_flag = nullptr;  // view: the last asynchronous build's word (KParams::list_flag)
   hipStream_t last_stream = nullptr;
   DevBuf<float4> d_tri;
   DevBuf<float> d_nrm;
@@ -249,9 +258,11 @@ struct rt_hip_ctx {
   uint32_t ext_total = 0;
   // phase timing (rt_hip_set_timing): per frame, events before the
   // candidate lists, before the render kernel and after it, on the render's
-  // stream; a ring of the last RT_TIMED_FRAMES frames
+  // stream; a ring of the last RT_TIMED_FRAMES frames.  A build on the side
+  // stream records ev[..][0] and its own end ev[..][5] there (ev_side)
   int timing = 0;
-  hipEvent_t ev[RT_TIMED_FRAMES][5] = {};  // lists | trace | shade | fold |
+  hipEvent_t ev[RT_TIMED_FRAMES][6] = {};  // lists | trace | shade | fold | ; [5]: a side-stream build's end
+  uint8_t ev_side[RT_TIMED_FRAMES] = {};
   unsigned long long frames = 0;  // timed frames recorded
 
   // the light buffers and the events; then the members: every buffer, and
@@ -259,6 +270,9 @@ struct rt_hip_ctx {
   ~rt_hip_ctx() {
     for (LBDevice* d : lb_dev) rt_lightbuf_free(d);
     if (ev_kept) (void)hipEventDestroy(ev_kept);
+    if (side_stream.s) (void)hipStreamSynchronize(side_stream);  // no build in flight past here
+    if (ev_lists_free) (void)hipEventDestroy(ev_lists_free);
+    if (ev_lists_done) (void)hipEventDestroy(ev_lists_done);
     for (auto& f : ev)
       for (hipEvent_t e : f)
         if (e) (void)hipEventDestroy(e);
@@ -267,6 +281,8 @@ struct rt_hip_ctx {
 
 // A setting that changes the lists (ListForecast::reset)
 static inline void lists_changed(rt_hip_ctx* c) {
+  if (c->overlap.in_flight && c->side_stream.s) (void)hipStreamSynchronize(c->side_stream);
+  c->overlap.joined();
   c->forecast.reset();
   c->pknown.valid = 0;
 }
@@ -316,6 +332,8 @@ int shadow_prepare(rt_hip_ctx* c, hipStream_t s);                               
 int lbuf_prepare(rt_hip_ctx* c, hipStream_t s);                                    // rt_hip.cpp
 int reflect_prepare(rt_hip_ctx* c, hipStream_t s);                                 // rt_hip.cpp
 int choose_accel(const rt_scene* s);                                               // rt_hip.cpp
-int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, int compat = 0);  // rt_lists.cpp
+// (from_render: rt_hip_render's own build, which may go to the side stream)
+int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, int compat = 0,
+                 bool from_render = false);  // rt_lists.cpp
 unsigned long long* cost_sum_of(rt_hip_ctx* c);                                    // rt_lists.cpp
 

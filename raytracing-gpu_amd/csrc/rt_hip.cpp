@@ -54,7 +54,19 @@ static int shade_tables(rt_hip_ctx* c, bool lights, bool materials) {
 extern "C" void rt_hip_destroy(rt_hip_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  delete c;
+  delete c;  // (waits for the side stream's build first: ~rt_hip_ctx)
+}
+
+extern "C" int rt_hip_set_overlap_lists(rt_hip_ctx* c, int enable) {
+  if (!c) return rt_set_error(RT_EINVAL, "null context");
+  c->overlap.set_enabled(enable != 0);
+  return RT_OK;
+}
+
+extern "C" int rt_hip_overlap_builds(const rt_hip_ctx* c, unsigned long long* n) {
+  if (!c || !n) return rt_set_error(RT_EINVAL, "null argument");
+  *n = c->overlap.side_builds;
+  return RT_OK;
 }
 
 // Per-node slack multipliers of the shadow walk for the context's culling
@@ -614,7 +626,10 @@ static int render_nothing(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hi
   c->cand_prims = c->cand_entries = c->cand_global = 0;
   c->d_cand_valid = nullptr;
   c->last_async = 0;
-  if (c->timing) HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
+  if (c->timing) {
+    HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
+    c->ev_side[c->frames % RT_TIMED_FRAMES] = 0;
+  }
   HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s));
   c->cost_hist.valid = 0;  // (the counters hold no trace's clocks now)
   return render_done(c, p, f, s, 1);
@@ -688,7 +703,11 @@ static int render_shadows(rt_hip_ctx* c, KParams& p, hipStream_t s) {
 static int render_lists(rt_hip_ctx* c, const rt_frame* f, KParams& p, bool use_ext, hipStream_t s) {
   c->cand_prims = c->cand_entries = c->cand_global = 0;
   c->d_cand_valid = nullptr;
-  if (c->timing) HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
+  c->list_flag = nullptr;
+  if (c->timing) {  // (a build on the side stream records its own start and end there)
+    HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
+    c->ev_side[c->frames % RT_TIMED_FRAMES] = 0;
+  }
   if (c->accel == RT_ACCEL_OCTREE && c->d_node && c->exact_camera) {
     if (use_ext) {  // the lists rt_hip_cand_consume built from the producers' entries
       p.cand_start = c->ext.cand_start;
@@ -704,7 +723,7 @@ static int render_lists(rt_hip_ctx* c, const rt_frame* f, KParams& p, bool use_e
       c->cand_global = c->ext.n_cand_global;
       c->cand_prims = 0;
     } else {
-      int rc = cand_prepare(c, f, &p, s);
+      int rc = cand_prepare(c, f, &p, s, 0, true);
       if (rc) return rc;
     }
   }
@@ -792,10 +811,21 @@ static int render_launch(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
   }
   p.frame_check = c->d_frame_check;
   // (bounds_kernel's copy of the build's counters)
-  p.list_flag = c->last_async ? c->d_cand_ctr + RT_CAND_CTR_SNAPSHOT + RT_CC_OVERFLOW : nullptr;
+  p.list_flag = c->last_async ? c->list_flag : nullptr;
   HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s));  // item streams, stats, record counters
   if (c->timing) HIP_TRY(hipEventRecord(ev[1], s));
   HIP_TRY(rt_launch_trace(&p, k.dacc, c->count_work, k.tpol, k.gt, s));
+  // the trace is the frame's last reader of the list buffers: the next
+  // frame's build may start behind it, beside the shade pass (csrc/rt_overlap.h)
+  if (p.cand_start && c->overlap.enabled) {
+    if (!c->side_stream.s) HIP_TRY(hipStreamCreateWithFlags(&c->side_stream.s, hipStreamNonBlocking));
+    if (!c->ev_lists_free) HIP_TRY(hipEventCreateWithFlags(&c->ev_lists_free, hipEventDisableTiming));
+    if (!c->ev_lists_done) HIP_TRY(hipEventCreateWithFlags(&c->ev_lists_done, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->ev_lists_free, s));
+    c->overlap.trace_launched();
+  } else {
+    c->overlap.lists_touched();
+  }
   if (p.item_cost) {
     c->cost_hist.set(f, rank, nranks);
     c->cost_waves = (uint32_t)k.gt;

@@ -445,7 +445,33 @@ static int cand_sort(rt_hip_ctx* c, uint32_t* keys, uint32_t* keys2, uint32_t* v
 // This rank's lists, built on this rank: cand_build for the rank's tiles
 // (every prim) -> radix sort by tile -> per-tile offsets -> per-entry skip
 // bounds -> work order.
-int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, int compat) {
+// A build of plan's shape for nt tiles allocates and frees nothing: every
+// buffer cand_build and cand_prepare size up front holds already (the
+// scans' temporaries and the partition counts grow by themselves, behind a
+// device-wide wait).
+static bool cand_buffers_fit(rt_hip_ctx* c, const ListPlan& plan, size_t nt) {
+  const size_t n = (size_t)plan.shape.total + 1;
+  return cand_scene_buffers(c, [](auto& b, size_t need) { return b.holds(need); }) &&
+         c->h_cand.holds(RT_CC_BUILD_WORDS) && (c->d_prim_leaf || !c->d_node) && c->d_cand_keys.holds(n) &&
+         c->d_cand_vals.holds(n) && c->d_cand_keys2.holds(n) && c->d_cand.holds(n) &&
+         c->d_cand_start.holds(nt + 1) && c->d_order.holds(3 * (nt + 1));
+}
+
+// Ends a side-stream build that did not reach its join (an error return in
+// the middle of cand_prepare): nothing stays in flight there.
+struct SideBuild {
+  rt_hip_ctx* c;
+  bool open = false;
+  ~SideBuild() {
+    if (!open) return;
+    (void)hipStreamSynchronize(c->side_stream);
+    c->overlap.joined();
+    c->overlap.lists_touched();
+  }
+};
+
+int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t cs, int compat, bool from_render) {
+  hipStream_t s = cs;  // the build's stream: the caller's, or the context's side stream (csrc/rt_overlap.h)
   CandParams cp;
   int rc = cand_params(f, c->scene_c, c->scene_r, c->cam_eps_ulps, c->bound_scale, kp->rank, kp->nranks,
                        &cp, compat);
@@ -461,6 +487,21 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   if (fc.snap_pending && arrived()) fc.absorb_snapshot(c->h_kept + RT_KEPT_CTR);
   const ListPlan plan = fc.plan(f, rank, nranks, c->async_lists, c->cand_store_fp, compat);
   const bool async = plan.async;
+  ListOverlap& ov = c->overlap;
+  SideBuild side{c};
+  if (ov.side(from_render, async, compat != 0, cand_buffers_fit(c, plan, nt)) && c->side_stream.s &&
+      c->ev_lists_free && c->ev_lists_done) {
+    s = c->side_stream;
+    HIP_TRY(hipStreamWaitEvent(s, c->ev_lists_free, 0));
+    side.open = true;
+    ov.forked();
+    if (c->timing) {  // the lists' own span, on their stream
+      HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][0], s));
+      c->ev_side[c->frames % RT_TIMED_FRAMES] = 1;
+    }
+  } else if (!from_render) {
+    ov.lists_touched();
+  }
   ListShape built;
   rc = cand_build(c, cp, s, 0, &total, &nglobal, async ? &plan.shape : nullptr, async ? nullptr : &built);
   if (rc) return rc;
@@ -541,6 +582,23 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, i
   c->d_cand_valid = (c->cand_refine || async) ? c->d_cand_start + nt : nullptr;
   c->cand_global = nglobal;
   c->cand_prims = 0;  // not counted separately (entries and globals are)
+  // the build's overflow flag for its frame's fold (bounds_kernel's snapshot
+  // of the counters): with the overlap on, in a word the next build -- which
+  // may run beside that fold -- does not write
+  c->list_flag = async ? c->d_cand_ctr + RT_CAND_CTR_SNAPSHOT + RT_CC_OVERFLOW : nullptr;
+  if (async && ov.enabled && !compat) {
+    if (!c->d_list_flag) HIP_TRY(c->d_list_flag.alloc(2));
+    uint32_t* const word = c->d_list_flag + ov.flag_slot();
+    HIP_TRY(hipMemcpyAsync(word, c->list_flag, sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    c->list_flag = word;
+  }
+  if (side.open) {  // the join: the caller's stream goes on behind the build
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev[c->frames % RT_TIMED_FRAMES][5], s));
+    HIP_TRY(hipEventRecord(c->ev_lists_done, s));
+    HIP_TRY(hipStreamWaitEvent(cs, c->ev_lists_done, 0));
+    side.open = false;
+    ov.joined();
+  }
   return RT_OK;
 }
 
@@ -558,6 +616,7 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
     return rt_set_error(RT_EINVAL, "no camera candidate lists in this configuration (octree, exact camera rays)");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  c->overlap.lists_touched();
   CandParams cp;
   int rc = cand_params(f, c->scene_c, c->scene_r, c->cam_eps_ulps, c->bound_scale, 0, 1, &cp, 0);
   if (rc) return rc;
@@ -654,6 +713,7 @@ extern "C" int rt_hip_cand_consume(rt_hip_ctx* c, const rt_frame* f, int rank, i
   const size_t nt = (size_t)rank_tile_count(f->width, f->height, rank, nranks);
   const uint32_t tpr = (uint32_t)rt_hip_tiles_per_rank(f->width, f->height, nranks);
   c->ext_ready = 0;  // set again once this consume's lists are complete
+  c->overlap.lists_touched();
   int rc = save_valid(c, s);
   if (rc) return rc;
   rc = cand_entry_buffers(c, n);

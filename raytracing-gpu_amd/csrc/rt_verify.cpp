@@ -136,8 +136,10 @@ extern "C" int rt_hip_frame_times(rt_hip_ctx* c, int n, float* lists_ms, float* 
   HIP_TRY(hipSetDevice(c->device));
   for (int i = 0; i < n; i++) {
     hipEvent_t* e = c->ev[(c->frames - (unsigned long long)n + (unsigned long long)i) % RT_TIMED_FRAMES];
+    const size_t slot = (size_t)((c->frames - (unsigned long long)n + (unsigned long long)i) % RT_TIMED_FRAMES);
     HIP_TRY(hipEventSynchronize(e[4]));
-    HIP_TRY(hipEventElapsedTime(lists_ms + i, e[0], e[1]));
+    // (a build on the side stream: its own span there, beside the previous frame's shade pass)
+    HIP_TRY(hipEventElapsedTime(lists_ms + i, e[0], c->ev_side[slot] ? e[5] : e[1]));
     HIP_TRY(hipEventElapsedTime(render_ms + i, e[1], e[4]));
   }
   return RT_OK;

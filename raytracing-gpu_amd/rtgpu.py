@@ -164,6 +164,8 @@ _PROTOS = [
     ("rt_hip_cand_verify_compat", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_cand_tile_entries", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("rt_hip_set_cand_item_cap", C.c_int, [C.c_void_p, C.c_uint]),
+    ("rt_hip_set_overlap_lists", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_hip_overlap_builds", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     ("rt_hip_verify_shadows", C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_ulonglong)]),
     ("rt_hip_verify_shadows_from", C.c_int, [C.c_void_p, C.c_uint, C.c_uint, C.POINTER(C.c_ulonglong)]),
     ("rt_hip_set_exact_camera", C.c_int, [C.c_void_p, C.c_int]),
@@ -661,6 +663,17 @@ class Context:
         """Test hook: cap the big footprints' emission work items (0: one
         wave per footprint, the fallback path)."""
         _check(lib().rt_hip_set_cand_item_cap(self.h, int(cap)), "cand_item_cap")
+
+    def set_overlap_lists(self, on=True):
+        """The next frame's list build beside the last frame's shade pass
+        (rt_hip_set_overlap_lists, default on; off for A/B runs)."""
+        _check(lib().rt_hip_set_overlap_lists(self.h, 1 if on else 0), "overlap_lists")
+
+    def overlap_builds(self):
+        """List builds of this context that ran on its second stream."""
+        n = C.c_ulonglong()
+        _check(lib().rt_hip_overlap_builds(self.h, C.byref(n)), "overlap_builds")
+        return int(n.value)
 
     def set_camera_slack(self, ulps):
         _check(lib().rt_hip_set_camera_slack(self.h, float(ulps)), "camera_slack")
