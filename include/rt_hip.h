@@ -18,6 +18,8 @@
  *   rt_hip_assemble()    (new)     tile buffers of all ranks -> PPM-order float image
  *   rt_hip_gbuffer()     (new)     opt-in per-sample passes of the last render: winning
  *                                  triangle, object, queries, depth, hit point, normal
+ *   rt_hip_trace_rays()  (new)     trace(ray, 1.0) of cpu/raytracer.c:19-34 for a batch of the
+ *                                  caller's rays: a colour and a hit record per ray
  *   rt_raytrace_multi()  (new)     in-process 1..8 GPU render + RCCL gather over xGMI
  *
  * Test, tuning and measurement hooks (probes, surveys, verification, A/B
@@ -369,6 +371,70 @@ int rt_hip_assemble_gbuffer(rt_hip_ctx *ctx, const rt_frame *frame, const void *
  * h_samples = H*W*4 records, PPM order. */
 int rt_hip_render_image_gbuffer(rt_hip_ctx *ctx, const rt_frame *frame, float *h_rgb,
                                 rt_gsample *h_samples, rt_stats *stats);
+
+/* Ray batches (new): trace rays the caller supplies instead of the pinhole
+ * camera's -- a panorama, an orthographic view, a light probe's faces, a pick
+ * ray, a line-of-sight query.  Ray i is (d_origins[3i..], d_dirs[3i..]),
+ * device memory of the context's device; the direction is used as given, not
+ * normalised (the reference's bounce directions are not either).
+ *
+ * rt_hip_trace_rays writes to d_rgb[3i..] the float channels of the
+ * reference's trace(ray_i, 1.0) (cpu/raytracer.c:19-34): its recursion, the
+ * coef < 0.01 cut-off, the bounce limit (rt_stats.depth_overflow, never
+ * silent) and the zero-normal rule, exactly as a camera sample's path; and to
+ * d_samples, if not NULL, n rt_gsample records (8-byte aligned) of the rays'
+ * first hits, the fields as above.  d_rgb == NULL with d_samples != NULL is a
+ * pure ray cast: one closest-hit query per ray, no bounce, no shade pass,
+ * queries == 1.  Both NULL: RT_EINVAL.  A ray with a non-finite component or
+ * an all-zero direction is not traced: colour 0, a miss of 0 queries.  n == 0
+ * returns RT_OK and writes nothing; n > RT_RAYS_MAX (what a hit record's index
+ * addresses) is RT_EINVAL.  Asynchronous on `stream`, with rt_hip_render's
+ * threading rules.  RT_EINVAL with a non-default traversal policy or
+ * rt_hip_set_count_work.
+ *
+ * Every query of a batch, the first included, is what a reflection ray's
+ * query is on this context: the per-lane octree walk at the culling slack
+ * (tested against brute force, not proven), the proven walk under
+ * rt_hip_set_exact_reflections, brute force on a FLAT context; no camera
+ * candidate lists.  The proven walk assumes |d| <= 1.0625: proven mode wants
+ * normalised directions, and a batch with a longer one still traces but
+ * rt_hip_stats returns RT_EINEXACT with closest_unproven counted.  With
+ * RT_RAYS_PACKET the first query of each aligned group of 64 rays walks the
+ * octree as one packet: a promise about the caller's ray order (coherent
+ * groups, e.g. rt_hip_frame_rays order 1) that only buys speed -- the results
+ * are the same bits with and without it; ignored under exact reflections and
+ * on FLAT.  Shadow rays start on scene triangles as always, so the light
+ * buffers and their proof apply unchanged.
+ *
+ * A batch uses the context's hit-record buffers (first sized for two records
+ * per ray): on overflow rt_hip_stats returns RT_EHITBUF, the buffers grow and
+ * the batch must be traced again, as a render.  rt_hip_stats after a batch:
+ * camera = rays traced, pixels = 0, cand_* = 0, every other counter as for a
+ * render; rt_hip_frame_check accounts a batch like a render.  A batch
+ * overwrites the last render's hit records: rt_hip_relight and rt_hip_gbuffer
+ * return RT_EINVAL after it until the next rt_hip_render.  It touches no
+ * candidate list, so a batch between two frames of a streaming caller leaves
+ * both frames as they are. */
+#define RT_RAYS_PACKET 1u   /* each aligned group of 64 rays walks its first query as one packet */
+#define RT_RAYS_MAX 0xfffffff8ull  /* 8 regions x (2^29 - 1) record slots */
+int rt_hip_trace_rays(rt_hip_ctx *ctx, const float *d_origins, const float *d_dirs, size_t n,
+                      unsigned flags, float *d_rgb, void *d_samples, void *stream);
+/* Upload, rt_hip_trace_rays on the context's stream, download, rt_hip_stats;
+ * synchronous.  Traces again once after RT_EHITBUF, as rt_hip_render_image. */
+int rt_hip_trace_rays_host(rt_hip_ctx *ctx, const float *h_origins, const float *h_dirs, size_t n,
+                           unsigned flags, float *h_rgb, rt_gsample *h_samples, rt_stats *stats);
+/* The 4 W H camera rays of `frame` (3 floats each), computed on the device by
+ * the arithmetic of the render's camera samples (cpu/raytracer.c:55-60).
+ * order 0: PPM pixel order, ray 4 (row W + col) + s, s in cpu sample order
+ * (rt_gsample above).  order 1: by 4x4-pixel quarter, quarters in scanline
+ * order, each aligned 64 rays one quarter's 16 pixels (row-major) x 4 samples,
+ * ray 64 quarter + 4 pixel + s -- the groups a render's trace walks as packets;
+ * width and height must be multiples of 4.  Odd sizes are RT_EINVAL. */
+int rt_hip_frame_rays(rt_hip_ctx *ctx, const rt_frame *frame, int order,
+                      float *d_origins, float *d_dirs, void *stream);
+/* rt_hip_frame_rays on the context's stream into host memory; synchronous. */
+int rt_hip_frame_rays_host(rt_hip_ctx *ctx, const rt_frame *frame, int order,
+                           float *h_origins, float *h_dirs);
 
 /* gpu/rt compatibility mode (gpu/raytracer.cu:31-129,
  * gpu/light.cu, gpu/colors.cu): the camera's frame rendered at 3x width and

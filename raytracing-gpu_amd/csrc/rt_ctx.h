@@ -9,6 +9,7 @@
 //                  of their host mirrors (rt_cand_host.cpp, which needs no context)
 //   rt_verify.cpp  probes, verification, timing and measurement hooks
 //   rt_multi.cpp   rt_raytrace_multi: N GPUs, RCCL exchange and gather
+//   rt_rays.cpp    rt_hip_trace_rays, rt_hip_frame_rays: a caller's ray batches
 // Internal, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include "rt_kernels.h"
 #include "rt_forecast.h"
 #include "rt_overlap.h"
+#include "rt_ray_items.h"
 #include "rt_lightbuf.h"
 #include "rt_mem.h"
 #include "rt_relight.h"
@@ -167,6 +169,7 @@ struct rt_hip_ctx {
   float lb_ulps = -1.0f;
   int lb_proven = -1;               // built proven (exact_shadows) or slack-grown
   unsigned long long lb_entry_cap = 0;  // test hook: fail builds past this many entries (0: none)
+  int last_batch = 0;               // the last launch was a ray batch (rt_hip_trace_rays): rt_hip_stats reports rays, no list
   KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here
   // exact shadow rays (csrc/rt_shadow.hip), built for the slack sh_ulps
   DevBuf<float2> d_prim_mu;
@@ -327,7 +330,16 @@ static inline void scene_extent(const rt_flat_scene& fs, float c[3], float* r) {
   }
 }
 
+// The kernels a render launches (render_kernels)
+struct RenderKernels {
+  int dacc, tpol, spol, gt, gs;
+};
+
 // shared between the files above (defined in the file named)
+int hit_buffers(rt_hip_ctx* c, size_t items, bool capture);                        // rt_hip.cpp
+void hit_views(const rt_hip_ctx* c, KParams& p);                                   // rt_hip.cpp
+int render_shadows(rt_hip_ctx* c, KParams& p, hipStream_t s);                      // rt_hip.cpp
+int render_kernels(rt_hip_ctx* c, KParams& p, long long items, hipStream_t s, RenderKernels* out);  // rt_hip.cpp
 int shadow_prepare(rt_hip_ctx* c, hipStream_t s);                                  // rt_hip.cpp
 int lbuf_prepare(rt_hip_ctx* c, hipStream_t s);                                    // rt_hip.cpp
 int reflect_prepare(rt_hip_ctx* c, hipStream_t s);                                 // rt_hip.cpp

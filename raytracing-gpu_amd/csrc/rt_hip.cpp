@@ -528,13 +528,13 @@ static int mask_buffer(rt_hip_ctx* c) {
   return RT_OK;
 }
 
-static int hit_buffers(rt_hip_ctx* c, size_t ntiles) {
-  const size_t items = 4 * ntiles;
+// (items: the trace's work items of 64 paths each -- 4 per tile of a frame,
+// rt_ray_item_count() of a ray batch; capture: the capturing trace's record
+// per (item, lane) too)
+int hit_buffers(rt_hip_ctx* c, size_t items, bool capture) {
   HIP_TRY(c->d_last.grow(items * 64, items * 64));
-  if (c->gbuffer) HIP_TRY(c->d_capture.grow(items * 64, items * 64));  // the capturing trace's record per (item, lane)
-  size_t want =(2 * items * 64 + RT_HIT_REGIONS - 1) / RT_HIT_REGIONS + 1024;
-  if (c->hit_need > want) want = c->hit_need;
-  if (want > (1ull << 29) - 1) want = (1ull << 29) - 1;  // slot field of a record index
+  if (capture) HIP_TRY(c->d_capture.grow(items * 64, items * 64));
+  const size_t want = rt_hit_region_records(items, c->hit_need);  // within the slot field of a record index
   if (want <= c->hit_cap()) return c->keep_visibility ? mask_buffer(c) : RT_OK;
   // all three or none: hit_cap() is what every one of them holds; the masks
   // of the records that go (rt_hip_set_keep_visibility, rt_hip_relight) with them
@@ -598,6 +598,7 @@ static void render_frame_params(KParams& p, const rt_hip_ctx* c, const rt_frame*
 // rt_hip_verify_shadows and rt_hip_gbuffer read afterwards.
 static int render_done(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hipStream_t s, int first_ev) {
   c->last_p = p;
+  c->last_batch = 0;
   if (c->gbuffer) {  // (an empty rank's rt_hip_gbuffer writes nothing either)
     c->gb_frame = *f;
     c->gb_valid = 1;
@@ -635,14 +636,8 @@ static int render_nothing(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hi
   return render_done(c, p, f, s, 1);
 }
 
-// The hit-record, capture and (work-counting pass) item-clock buffers.
-static int render_buffers(rt_hip_ctx* c, KParams& p) {
-  {
-    int rc = hit_buffers(c, (size_t)p.ntiles_local);
-    if (rc) return rc;
-  }
-  if (c->gbuffer) p.capture = c->d_capture;
-  if (c->keep_visibility) p.hit_lit = c->d_hit_lit;  // the shade pass keeps each record's mask (rt_hip_relight)
+// The kernels' views of the hit-record buffers and their counters.
+void hit_views(const rt_hip_ctx* c, KParams& p) {
   p.hit = c->d_hit;
   p.hit_prev = c->d_hit_prev;
   p.hit_term = c->d_hit_term;
@@ -650,6 +645,17 @@ static int render_buffers(rt_hip_ctx* c, KParams& p) {
   p.shade_counter = c->d_hit_count + RT_HIT_REGIONS * RT_HIT_STRIDE;
   p.hit_cap = (uint32_t)c->hit_cap();
   p.last = c->d_last;
+}
+
+// The hit-record, capture and (work-counting pass) item-clock buffers.
+static int render_buffers(rt_hip_ctx* c, KParams& p) {
+  {
+    int rc = hit_buffers(c, RT_TILE_ITEMS * (size_t)p.ntiles_local, c->gbuffer != 0);
+    if (rc) return rc;
+  }
+  if (c->gbuffer) p.capture = c->d_capture;
+  if (c->keep_visibility) p.hit_lit = c->d_hit_lit;  // the shade pass keeps each record's mask (rt_hip_relight)
+  hit_views(c, p);
   if (c->count_work) {  // per-item clocks of the instrumented pass (rt_hip_tile_cycles)
     const size_t items = 4 * (size_t)p.ntiles_local;
     HIP_TRY(c->d_tile_cycles.grow(6 * items, 6 * items));
@@ -661,7 +667,7 @@ static int render_buffers(rt_hip_ctx* c, KParams& p) {
 
 // What the shadow queries need: light buffers, the proven walk's multipliers,
 // the off-box queries' queue.
-static int render_shadows(rt_hip_ctx* c, KParams& p, hipStream_t s) {
+int render_shadows(rt_hip_ctx* c, KParams& p, hipStream_t s) {
   {
     // light buffers, proven in exact-shadow mode (no-op unless the slack or
     // the mode changed); the staged policies walk
@@ -731,13 +737,10 @@ static int render_lists(rt_hip_ctx* c, const rt_frame* f, KParams& p, bool use_e
   return RT_OK;
 }
 
-// The kernels a render launches: the device acceleration structure, the
-// trace and shade kernels' policies (their instantiations) and grids.
-struct RenderKernels {
-  int dacc, tpol, spol, gt, gs;
-};
-
-static int render_kernels(rt_hip_ctx* c, KParams& p, hipStream_t s, RenderKernels* out) {
+// The kernels a render launches (RenderKernels, rt_ctx.h): the device
+// acceleration structure, the trace and shade kernels' policies (their
+// instantiations) and grids, for `items` work items of the trace.
+int render_kernels(rt_hip_ctx* c, KParams& p, long long items, hipStream_t s, RenderKernels* out) {
   // an empty octree scene has nothing to traverse: the FLAT kernels with 0
   // records are exact (their grids are the FLAT instantiation's own)
   const bool empty = c->accel == RT_ACCEL_OCTREE && !c->d_node;
@@ -774,7 +777,6 @@ static int render_kernels(rt_hip_ctx* c, KParams& p, hipStream_t s, RenderKernel
   // thousand items -- C1 has 4,096).  The shade kernel's records are not
   // known before the trace, at least one 64-record chunk per item is assumed
   {
-    const long long items = 4ll * p.ntiles_local;
     if (items < gt) gt = (int)items;
     if (items < gs) gs = (int)items;
   }
@@ -857,7 +859,8 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   if (p.ntiles_local == 0) return render_nothing(c, p, f, s);
   RenderKernels k;
   if ((rc = render_buffers(c, p)) || (rc = render_shadows(c, p, s)) || (rc = render_lists(c, f, p, use_ext, s)) ||
-      (rc = render_kernels(c, p, s, &k)) || (rc = render_launch(c, f, rank, nranks, p, k, s)))
+      (rc = render_kernels(c, p, RT_TILE_ITEMS * (long long)p.ntiles_local, s, &k)) ||
+      (rc = render_launch(c, f, rank, nranks, p, k, s)))
     return rc;
   return render_done(c, p, f, s, 4);
 }
@@ -871,12 +874,16 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   HIP_TRY(hipMemcpyAsync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(hc, c->d_hit_count, sizeof hc, hipMemcpyDeviceToHost, s));
   uint32_t valid = 0, actr[RT_CC_BUILD_WORDS] = {};
-  if (c->d_cand_valid) HIP_TRY(hipMemcpyAsync(&valid, c->d_cand_valid, sizeof valid, hipMemcpyDeviceToHost, s));
-  const int was_async = c->last_async;
+  // a ray batch (rt_hip_trace_rays) used no list: a frame's list counts stay
+  // where they are for that frame's own readers, and the batch reports none
+  const bool batch = c->last_batch != 0;
+  if (c->d_cand_valid && !batch)
+    HIP_TRY(hipMemcpyAsync(&valid, c->d_cand_valid, sizeof valid, hipMemcpyDeviceToHost, s));
+  const int was_async = batch ? 0 : c->last_async;
   if (was_async)
     HIP_TRY(hipMemcpyAsync(actr, c->d_cand_ctr + RT_CAND_CTR_SNAPSHOT, sizeof actr, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (c->d_cand_valid) {
+  if (c->d_cand_valid && !batch) {
     c->cand_entries = valid;
     c->d_cand_valid = nullptr;
   }
@@ -903,9 +910,14 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   for (int k = 0; k < RT_NSTATS; k++) out->*rt_stat_member[k] = h[k];
   out->camera = 4 * h[RT_ST_PIXELS];
   out->hit_records = records;
-  out->cand_prims = c->cand_prims;
-  out->cand_entries = c->cand_entries;
-  out->cand_global = c->cand_global;
+  if (batch) {  // the rays traced, counted in the pixels' slot; no pixel, no list
+    out->camera = h[RT_ST_PIXELS];
+    out->pixels = 0;
+  } else {
+    out->cand_prims = c->cand_prims;
+    out->cand_entries = c->cand_entries;
+    out->cand_global = c->cand_global;
+  }
   if (need > c->hit_cap()) {  // the frame is incomplete: grow for the next render
     c->hit_need = need + need / 4 + 1024;
     return rt_set_error(RT_EHITBUF, "%llu hit records, %zu per region held (grown to %zu: render again)",
@@ -1168,7 +1180,8 @@ extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
   if (rc) return rc;
   p.hit_lit = c->d_hit_lit;
   RenderKernels k;
-  if ((rc = render_shadows(c, p, s)) || (rc = render_kernels(c, p, s, &k))) return rc;
+  if ((rc = render_shadows(c, p, s)) || (rc = render_kernels(c, p, RT_TILE_ITEMS * (long long)p.ntiles_local, s, &k)))
+    return rc;
   const RelightWork w = c->relight.work(light_table(c));
   if (w.path == RT_RELIGHT_RECOLOUR) p.oob = nullptr;  // no query, so none deferred: no fixup
   // every device pointer the kernels will follow must exist (a null one
@@ -1356,6 +1369,7 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
     if (rc) return rc;
   }
   c->cost_hist.valid = 0;  // the counters are the compat render's
+  c->last_batch = 0;
   c->rl_valid = 0;         // (and no hit records are kept: nothing to relight)
   c->relight.invalidate();
   if (hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s) != hipSuccess ||

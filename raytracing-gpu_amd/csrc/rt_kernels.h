@@ -83,7 +83,14 @@
 // sample (KParams::capture) -- the default kernel has no register to spare
 // for it, so it has no switch either
 #define RT_POLICY_GBUFFER 6
-#define RT_NPOLICIES 7
+// ray-batch trace kernels only (rt_hip_trace_rays, csrc/rt_rays.h), chosen by
+// the host: every query of a path, the first included, takes the route of a
+// reflection ray -- no camera candidate lists, the secondary rays' slack, the
+// walk the batch names (RayArgs::walk).  RAYS_GB also fills a capture record
+// per ray (KParams::capture) and can stop after the first query (a ray cast)
+#define RT_POLICY_RAYS 7
+#define RT_POLICY_RAYS_GB 8
+#define RT_NPOLICIES 9
 // words of one public G-buffer sample record (include/rt_hip.h rt_gsample)
 #define RT_GB_WORDS_D 10
 
@@ -207,6 +214,21 @@ struct KParams {
 };
 // (the bits of frame_check[0], RT_FRAME_*: rt_counters.h)
 
+// What a ray batch's kernels take beside the KParams (csrc/rt_rays.h): its own
+// small block, so KParams -- passed by value to every kernel -- stays as it is.
+#define RT_RAYS_WALK_PACKET 1u  // the first query of each work item as one staged packet
+#define RT_RAYS_WALK_EXACT 2u   // every query through the proven reflection walk (KParams::node_rf)
+#define RT_RAYS_WALK_CAST 4u    // stop after the first query (RT_POLICY_RAYS_GB)
+struct RayArgs {
+  const float* org;      // 3 floats per ray
+  const float* dir;      // 3 floats per ray, used as given
+  unsigned long long n;  // rays
+  uint32_t nitems;       // rt_ray_item_count(n)
+  uint32_t walk;         // RT_RAYS_WALK_*
+  float* rgb;            // 3 floats per ray (NULL: a ray cast)
+  uint32_t* samples;     // RT_GB_WORDS_D words per ray (NULL: none)
+};
+
 // The three launches of one render (policy = RT_POLICY_*, octree only):
 // trace (closest hits -> hit records), shade (shadow queries + Phong per
 // record -> terms), fold (terms -> the rank's tile buffer)
@@ -243,6 +265,17 @@ extern "C" hipError_t rt_launch_probe_shadow(const KParams* p, const float* org,
 // The walk's spill area p->spill holds `grid` waves: n <= 64 grid.
 extern "C" hipError_t rt_launch_probe_closest(const KParams* p, const float* org, const float* dir, uint32_t n,
                                               uint32_t nprim, int brute, uint32_t* out, int grid, hipStream_t stream);
+// A ray batch (csrc/rt_rays.h): its trace (policy = RT_POLICY_RAYS or
+// RT_POLICY_RAYS_GB, one-wave workgroups pulling items of 64 rays), the fold of
+// every ray's path into a->rgb with the frame check's bookkeeping (a->rgb NULL:
+// the bookkeeping alone), and the capture records turned into a->samples
+extern "C" hipError_t rt_launch_rays_trace(const KParams* p, const RayArgs* a, int accel, int policy, int grid,
+                                           hipStream_t stream);
+extern "C" hipError_t rt_launch_rays_fold(const KParams* p, const RayArgs* a, hipStream_t stream);
+extern "C" hipError_t rt_launch_rays_samples(const KParams* p, const RayArgs* a, hipStream_t stream);
+// rt_hip_frame_rays: the 4 W H camera rays of p's frame (p->u, v, C, pos, W, H)
+// in pixel order (order 0) or quarter order (1), csrc/rt_ray_items.h
+extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* org, float* dir, hipStream_t stream);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

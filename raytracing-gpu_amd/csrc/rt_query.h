@@ -87,6 +87,32 @@ __device__ __forceinline__ void closest_q(const KParams& p, const Ray& r, bool a
   }
 }
 
+// Closest-hit query of a ray batch (RT_POLICY_RAYS*, csrc/rt_rays.h): what a
+// reflection ray's query is on this context -- brute force on FLAT, the proven
+// walk under RT_RAYS_WALK_EXACT, else the per-lane slack walk -- and, when the
+// batch asks for it, the first query of a work item as one staged packet (the
+// walk RT_POLICY_STAGED runs for arbitrary rays, at the same slack).  walk is
+// wave-uniform (RayArgs::walk).  Converged call, act = lane has a query.
+template <int ACCEL>
+__device__ __forceinline__ void rays_closest(const KParams& p, const Ray& r, bool act, int depth, uint32_t walk,
+                                             Best& b, Stack& s, WaveCtx& w, WorkCount& wc) {
+  if (ACCEL == RT_ACCEL_FLAT_D) {
+    closest_q<ACCEL, false, RT_POLICY_DEFAULT>(p, r, act, depth, b, s, w, wc);
+    return;
+  }
+  if (walk & RT_RAYS_WALK_EXACT) {
+    LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act) oct_closest_rf<false>(p, r, b, s, lc);
+    absorb<false>(wc, lc, false);
+  } else if ((walk & RT_RAYS_WALK_PACKET) && depth == 0) {
+    staged_closest<false>(p, r, act, b, w, wc);
+  } else {
+    LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (act) oct_closest<false>(p, r, b, s, lc);
+    absorb<false>(wc, lc, false);
+  }
+}
+
 // Shadow query through the light's buffer (built by csrc/rt_lightbuf.hip; the
 // listing it relies on: csrc/rt_lightbuf_geom.h): the
 // triangles listed in the cell the ray's origin projects to, in key order,

@@ -101,20 +101,12 @@ __device__ __forceinline__ size_t rec_addr(const KParams& p, uint32_t idx) {
   return (size_t)(idx & 7u) * p.hit_cap + (idx >> 3);
 }
 
-// The camera sample of lane `lane` of item q of rank-local tile t (its pixel
-// and sample smp by rt_item_pixel): its ray (origin on the film, direction
-// towards the eye) exactly as cpu/raytracer.c:55-60 computes it; false when
-// the lane's pixel lies outside the framebuffer's even-sized area (its ray is
-// still defined).
-__device__ __forceinline__ bool camera_sample(const KParams& p, uint32_t t, uint32_t q, int lane, int& smp,
-                                              f3& point, f3& dir) {
-  int row, col, pr, pc;
-  // (the lane's share of the map does not change from item to item: opaque,
-  // or it is hoisted out of trace_kernel's item loop and holds registers
-  // across every walk -- 8 B more scratch per lane)
-  asm volatile("" : "+v"(lane));
-  rt_item_pixel(q, (uint32_t)lane, &row, &col, &smp);
-  tile_pixel(p, t, row, col, pr, pc);
+// Sample smp of the pixel at PPM (row pr, column pc): its ray (origin on the
+// film, direction towards the eye) exactly as cpu/raytracer.c:55-60 computes
+// it; false when the pixel lies outside the framebuffer's even-sized area (its
+// ray is still defined).  The one place the camera's arithmetic is written:
+// trace_kernel's samples and rt_hip_frame_rays' generator (rt_rays.h) call it.
+__device__ __forceinline__ bool camera_ray(const KParams& p, int pr, int pc, int smp, f3& point, f3& dir) {
   // PPM (row, col) -> framebuffer slot (j, i) of cpu/raytracer.c:71,128-134
   const int ii = p.W - pc, jj = p.H - pr;
   const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 && jj <= 2 * (p.H / 2);
@@ -125,6 +117,20 @@ __device__ __forceinline__ bool camera_sample(const KParams& p, uint32_t t, uint
   point = add(add(p.C, scale(p.u, k)), scale(p.v, l));
   dir = normalize(sub(p.pos, point));
   return valid;
+}
+
+// The camera sample of lane `lane` of item q of rank-local tile t (its pixel
+// and sample smp by rt_item_pixel).
+__device__ __forceinline__ bool camera_sample(const KParams& p, uint32_t t, uint32_t q, int lane, int& smp,
+                                              f3& point, f3& dir) {
+  int row, col, pr, pc;
+  // (the lane's share of the map does not change from item to item: opaque,
+  // or it is hoisted out of trace_kernel's item loop and holds registers
+  // across every walk -- 8 B more scratch per lane)
+  asm volatile("" : "+v"(lane));
+  rt_item_pixel(q, (uint32_t)lane, &row, &col, &smp);
+  tile_pixel(p, t, row, col, pr, pc);
+  return camera_ray(p, pr, pc, smp, point, dir);
 }
 
 // A lane's G-buffer capture record (KParams::capture), as initialised: no
@@ -140,14 +146,18 @@ struct Capture {
 // recursion as a wave-uniform bounce loop, a hit record appended per hit (one
 // atomic per wave and bounce, on the item stream's own counter x).  Returns
 // the lane's deepest record (RT_NO_REC: none).  valid = the lane owns a pixel.
-// RT_POLICY_GBUFFER only: cap = the lane's capture record (KParams::capture),
-// filled at the camera query (depth 0), its query count on every bounce.
+// RT_POLICY_GBUFFER and RT_POLICY_RAYS_GB only: cap = the lane's capture record
+// (KParams::capture), filled at the first query (depth 0), its query count on
+// every bounce.  RT_POLICY_RAYS*: a caller's rays (rt_rays.h) -- the first query
+// takes a reflection ray's route too (rays_closest with the batch's `walk`, the
+// secondary slack, no candidate lists), and a ray cast ends after it.
 template <int ACCEL, bool COUNT, int POL>
 __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 o, f3 d,
                                                uint32_t x, Stack& s, WaveCtx& w, WorkCount& wc,
                                                uint32_t tile, Capture& cap, int depth = 0, float coef = 1.0f,
-                                               uint32_t prev = RT_NO_REC) {
-  constexpr bool kCapture = POL == RT_POLICY_GBUFFER;
+                                               uint32_t prev = RT_NO_REC, uint32_t walk = 0) {
+  constexpr bool kRays = POL == RT_POLICY_RAYS || POL == RT_POLICY_RAYS_GB;
+  constexpr bool kCapture = POL == RT_POLICY_GBUFFER || POL == RT_POLICY_RAYS_GB;
   // depth: wave-uniform, queries so far on this path
   bool alive = valid;
   for (;;) {
@@ -156,7 +166,7 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     if (am == 0) break;
     wc.closest += (uint32_t)__popcll(am);  // wave-uniform counters (SGPRs)
     if (kCapture && alive) cap.queries++;  // the lane's own share of wc.closest
-    Ray r = make_ray(p, o, d, depth == 0 ? p.eps_rel_cam : p.eps_rel);
+    Ray r = make_ray(p, o, d, depth == 0 && !kRays ? p.eps_rel_cam : p.eps_rel);
     Best b;
     b.dist = __builtin_inff();
     b.t_cut = __builtin_inff();
@@ -165,13 +175,16 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     b.u = b.v = 0.0f;
     b.t = 0.0f;
     uint64_t c0 = COUNT ? __builtin_readcyclecounter() : 0ull;
-    closest_q<ACCEL, COUNT, POL>(p, r, alive, depth, b, s, w, wc);
+    if constexpr (kRays)
+      rays_closest<ACCEL>(p, r, alive, depth, walk, b, s, w, wc);
+    else
+      closest_q<ACCEL, COUNT, POL>(p, r, alive, depth, b, s, w, wc);
     if (COUNT) {
       const uint64_t c1 = __builtin_readcyclecounter();
       (depth == 0 ? wc.cy_cam : wc.cy_sec) += (uint32_t)(c1 - c0);
       c0 = c1;
     }
-    if (ACCEL != RT_ACCEL_FLAT_D && depth == 0) cand_closest<COUNT>(p, r, alive, tile, b, w, wc);
+    if (!kRays && ACCEL != RT_ACCEL_FLAT_D && depth == 0) cand_closest<COUNT>(p, r, alive, tile, b, w, wc);
     if (COUNT) wc.cy_cand += (uint32_t)(__builtin_readcyclecounter() - c0);
     bool hit = alive && b.dist != __builtin_inff();
     if (kCapture && depth == 0 && hit) {  // the camera query's winner, a zero-normal one included
@@ -218,6 +231,7 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     wc.overflow += (uint32_t)__popcll(__ballot(deep));
     alive = hit && depth + 1 < RT_MAX_BOUNCES;
     ++depth;
+    if (POL == RT_POLICY_RAYS_GB && (walk & RT_RAYS_WALK_CAST)) break;  // a ray cast: its first query only
   }
   return prev;
 }
@@ -599,29 +613,34 @@ namespace rt {
 // on C3, beside shade's 1.84 -> 1.69 from the same order.  One thread per
 // (item, lane) with the samples brought together by __shfl read them side by
 // side but ran four times the threads: 0.245 and 0.076 ms)
+// The frame check's bookkeeping (KParams::frame_check), by one thread of a
+// frame's or a ray batch's last launch: every earlier launch has ended (same
+// stream).
+__device__ __forceinline__ void frame_check_account(const KParams& p) {
+  uint32_t f = 0;
+  for (int x = 0; x < RT_HIT_REGIONS; x++)
+    if (p.hit_count[RT_HIT_STRIDE * x] > p.hit_cap) f |= RT_FRAME_HITBUF;
+  unsigned long long s[RT_NSTATS] = {};
+  for (int set = 0; set < RT_STAT_SETS; set++)
+    for (int k = 0; k < RT_NSTATS; k++) s[k] += p.stats[set * RT_STAT_STRIDE + k];
+  auto raised = [&s](uint32_t flag) {  // a slot that raises `flag` is not zero
+    bool any = false;
+    for (uint32_t k = 0; k < RT_NSTATS; k++) any = any || (rt_stat_frame_flag(k) == flag && s[k]);
+    return any;
+  };
+  if (raised(RT_FRAME_DEPTH)) f |= RT_FRAME_DEPTH;
+  if (raised(RT_FRAME_ZERO)) f |= RT_FRAME_ZERO;
+  if (raised(RT_FRAME_UNPROVEN) || (p.oob_count && *p.oob_count > p.oob_cap)) f |= RT_FRAME_UNPROVEN;
+  if (p.list_flag && *p.list_flag) f |= RT_FRAME_LISTS;
+  atomicOr(p.frame_check, (unsigned long long)f);
+  atomicAdd(p.frame_check + 1, 1ull);
+  atomicAdd(p.frame_check + 2, s[RT_ST_CLOSEST]);
+  atomicAdd(p.frame_check + 3, s[RT_ST_SHADOW]);
+}
+
 __global__ __launch_bounds__(256) void fold_kernel(KParams p) {
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx == 0 && p.frame_check) {  // every earlier launch of the frame has ended (same stream)
-    uint32_t f = 0;
-    for (int x = 0; x < RT_HIT_REGIONS; x++)
-      if (p.hit_count[RT_HIT_STRIDE * x] > p.hit_cap) f |= RT_FRAME_HITBUF;
-    unsigned long long s[RT_NSTATS] = {};
-    for (int set = 0; set < RT_STAT_SETS; set++)
-      for (int k = 0; k < RT_NSTATS; k++) s[k] += p.stats[set * RT_STAT_STRIDE + k];
-    auto raised = [&s](uint32_t flag) {  // a slot that raises `flag` is not zero
-      bool any = false;
-      for (uint32_t k = 0; k < RT_NSTATS; k++) any = any || (rt_stat_frame_flag(k) == flag && s[k]);
-      return any;
-    };
-    if (raised(RT_FRAME_DEPTH)) f |= RT_FRAME_DEPTH;
-    if (raised(RT_FRAME_ZERO)) f |= RT_FRAME_ZERO;
-    if (raised(RT_FRAME_UNPROVEN) || (p.oob_count && *p.oob_count > p.oob_cap)) f |= RT_FRAME_UNPROVEN;
-    if (p.list_flag && *p.list_flag) f |= RT_FRAME_LISTS;
-    atomicOr(p.frame_check, (unsigned long long)f);
-    atomicAdd(p.frame_check + 1, 1ull);
-    atomicAdd(p.frame_check + 2, s[RT_ST_CLOSEST]);
-    atomicAdd(p.frame_check + 3, s[RT_ST_SHADOW]);
-  }
+  if (idx == 0 && p.frame_check) frame_check_account(p);
   if (idx >= (uint32_t)p.ntiles_local * 64u) return;
   const uint32_t t = idx >> 6, lane = idx & 63u;
   int pr, pc;
@@ -698,29 +717,14 @@ __global__ __launch_bounds__(256) void assemble_words_kernel(const uint32_t* __r
   out[idx] = tiles[(((size_t)rank * tiles_per_rank + local) * 64 + lane) * (size_t)words + k];
 }
 
-// The G-buffer of a render traced with RT_POLICY_GBUFFER (p = its KParams):
-// one thread per (pixel slot, sample) of the rank's tiles turns the sample's
-// capture record and its path's first hit record into the public record
-// (include/rt_hip.h rt_gsample: prim obj queries dist P N) at words
-// [RT_GB_WORDS_D * (4 * slot + sample), ...) of `out` -- consecutive threads
-// write consecutive records, five 8-byte stores each.  Padding slots and
-// pixels outside the framebuffer's even-sized area (fold_kernel's test) are
-// misses without a query.
-__global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __restrict__ out) {
-  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (size_t)p.ntiles_local * 256u) return;
-  const uint32_t slot = (uint32_t)(g >> 2), smp = (uint32_t)g & 3u;
-  const uint32_t t = slot >> 6, lane = slot & 63u;
-  int pr, pc;
-  const int row = (int)(lane >> 3), col_ = (int)(lane & 7u);
-  tile_pixel(p, t, row, col_, pr, pc);
-  const int ii = p.W - pc, jj = p.H - pr;
-  const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 &&
-                     jj <= 2 * (p.H / 2);
+// The public record (include/rt_hip.h rt_gsample: prim obj queries dist P N)
+// of capture record `slot` (KParams::capture) and its path's first hit record,
+// as five 8-byte stores at `out`; valid = false: a miss without a query.
+__device__ __forceinline__ void gsample_store(const KParams& p, bool valid, size_t slot, uint32_t* out) {
   uint32_t prim = 0xffffffffu, obj = 0xffffffffu, queries = 0, dist = 0x7f800000u;
   float4 h0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), h1 = h0;
   if (valid) {
-    const uint4 c = p.capture[rt_item_slot(t, row, col_, (int)smp)];
+    const uint4 c = p.capture[slot];
     queries = c.w;
     if (c.x != 0xffffffffu) {
       prim = c.x;
@@ -734,7 +738,7 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
       }
     }
   }
-  uint2* o = (uint2*)(out + g * RT_GB_WORDS_D);
+  uint2* o = (uint2*)out;
   o[0] = make_uint2(prim, obj);
   o[1] = make_uint2(queries, dist);
   o[2] = make_uint2(__float_as_uint(h0.x), __float_as_uint(h0.y));
@@ -742,10 +746,31 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
   o[4] = make_uint2(__float_as_uint(h1.x), __float_as_uint(h1.y));
 }
 
+// The G-buffer of a render traced with RT_POLICY_GBUFFER (p = its KParams):
+// one thread per (pixel slot, sample) of the rank's tiles turns the sample's
+// capture record and its path's first hit record into the public record at
+// words [RT_GB_WORDS_D * (4 * slot + sample), ...) of `out` -- consecutive
+// threads write consecutive records.  Padding slots and pixels outside the
+// framebuffer's even-sized area (fold_kernel's test) are misses without a query.
+__global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __restrict__ out) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (size_t)p.ntiles_local * 256u) return;
+  const uint32_t slot = (uint32_t)(g >> 2), smp = (uint32_t)g & 3u;
+  const uint32_t t = slot >> 6, lane = slot & 63u;
+  int pr, pc;
+  const int row = (int)(lane >> 3), col_ = (int)(lane & 7u);
+  tile_pixel(p, t, row, col_, pr, pc);
+  const int ii = p.W - pc, jj = p.H - pr;
+  const bool valid = pr < p.H && pc < p.W && ii >= 1 && ii <= 2 * (p.W / 2) && jj >= 1 &&
+                     jj <= 2 * (p.H / 2);
+  gsample_store(p, valid, rt_item_slot(t, row, col_, (int)smp), out + g * RT_GB_WORDS_D);
+}
+
 }  // namespace rt
 
 #include "rt_recolour.h"  // relight_zero_kernel, recolour_kernel: after every render kernel
 #include "rt_shade_tables.h"  // shade_tables_kernel: after those
+#include "rt_rays.h"  // the ray batches' kernels: after those
 
 // ---------------------------------------------------------------- launchers
 // One instantiation per (kernel, accel, work counting, policy); the default
@@ -795,9 +820,21 @@ static const void* kernel_of(int accel, int count_work, int policy) {
 // Persistent grid of a kernel: as many one-wave workgroups as the kernel's
 // registers and LDS let every CU hold (the occupancy API), so every SIMD is
 // filled and no workgroup waits for a slot.
+// The ray batches' trace instantiation (rt_rays.h): policy RT_POLICY_RAYS or
+// RT_POLICY_RAYS_GB; no counting variant.
+static const void* rays_kernel_of(int accel, int policy) {
+  using namespace rt;
+  if (policy == RT_POLICY_RAYS_GB)
+    return accel == RT_ACCEL_FLAT_D ? (const void*)rays_trace_kernel<RT_ACCEL_FLAT_D, RT_POLICY_RAYS_GB>
+                                    : (const void*)rays_trace_kernel<RT_ACCEL_OCTREE_D, RT_POLICY_RAYS_GB>;
+  return accel == RT_ACCEL_FLAT_D ? (const void*)rays_trace_kernel<RT_ACCEL_FLAT_D, RT_POLICY_RAYS>
+                                  : (const void*)rays_trace_kernel<RT_ACCEL_OCTREE_D, RT_POLICY_RAYS>;
+}
+
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid) {
-  const void* k = trace ? kernel_of<true>(accel, count_work, policy)
+  const bool rays = policy == RT_POLICY_RAYS || policy == RT_POLICY_RAYS_GB;
+  const void* k = trace ? (rays ? rays_kernel_of(accel, policy) : kernel_of<true>(accel, count_work, policy))
                         : kernel_of<false>(accel, count_work, policy);
   int per_cu = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 64, 0);
@@ -939,5 +976,35 @@ extern "C" hipError_t rt_launch_shade_tables(const float* light, uint32_t nlight
   if (!n) return hipSuccess;
   hipLaunchKernelGGL((rt::shade_tables_kernel<0>), dim3((n + 255) / 256), dim3(256), 0, stream, light, nlight, lshade,
                      mat, nobj, mshade);
+  return hipGetLastError();
+}
+
+// A ray batch's launches (rt_kernels.h, csrc/rt_rays.h).  After the relight's,
+// for the same reason: every earlier kernel keeps its place.
+extern "C" hipError_t rt_launch_rays_trace(const KParams* p, const RayArgs* a, int accel, int policy, int grid,
+                                           hipStream_t stream) {
+  if (grid <= 0) return hipErrorInvalidValue;
+  void* args[] = {(void*)p, (void*)a};
+  return hipLaunchKernel(rays_kernel_of(accel, policy), dim3(grid), dim3(64), args, 0, stream);
+}
+
+extern "C" hipError_t rt_launch_rays_fold(const KParams* p, const RayArgs* a, hipStream_t stream) {
+  const unsigned long long blocks = a->rgb ? (a->n + 255) / 256 : 1;
+  if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((rt::rays_fold_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *p, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_rays_samples(const KParams* p, const RayArgs* a, hipStream_t stream) {
+  const unsigned long long blocks = (a->n + 255) / 256;
+  if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((rt::rays_sample_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *p, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* org, float* dir, hipStream_t stream) {
+  const unsigned long long blocks = (4ull * (unsigned long long)p->W * (unsigned long long)p->H + 255) / 256;
+  if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((rt::frame_rays_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *p, order, org, dir);
   return hipGetLastError();
 }

@@ -214,6 +214,12 @@ _PROTOS = [
                                           C.c_void_p]),
     ("rt_hip_render_image_gbuffer", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.c_void_p,
                                               C.POINTER(Stats)]),
+    ("rt_hip_trace_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    ("rt_hip_trace_rays_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
+                                         C.c_void_p, C.POINTER(Stats)]),
+    ("rt_hip_frame_rays", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_frame_rays_host", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_void_p, C.c_void_p]),
     ("rt_hip_malloc", C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("rt_hip_free", C.c_int, [C.c_void_p]),
     ("rt_hip_memcpy_d2h", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -493,6 +499,110 @@ def coverage(samples):
     """(H, W) float32 alpha in {0, 1/4, 1/2, 3/4, 1}: the share of each pixel's
     four samples whose camera ray hit geometry."""
     return ((samples["prim"] >= 0).sum(axis=-1) * 0.25).astype(np.float32)
+
+
+# ---- ray batches (include/rt_hip.h rt_hip_trace_rays, rt_hip_frame_rays) ----
+RT_RAYS_PACKET = 1
+RAY_ORDER = {"pixel": 0, "quarter": 1}
+
+
+def quarter_order(width, height):
+    """(perm, inv) of rt_hip_frame_rays' quarter order (csrc/rt_ray_items.h
+    rt_quarter_order_ray): perm[k] = the pixel-order index 4 (row W + col) + s
+    of quarter-order ray k, inv its inverse.  Each aligned 64 rays are one
+    4x4-pixel quarter (quarters in scanline order), lane = 4 (4 r + c) + s
+    (csrc/rt_tiles.h rt_item_pixel).  width, height: multiples of 4."""
+    if width <= 0 or height <= 0 or width % 4 or height % 4:
+        raise ValueError(f"quarter order needs multiples of 4, not {width}x{height}")
+    k = np.arange(4 * width * height, dtype=np.int64)
+    quarter, lane = k // 64, k % 64
+    px, smp = lane >> 2, lane & 3
+    row = 4 * (quarter // (width // 4)) + (px >> 2)
+    col = 4 * (quarter % (width // 4)) + (px & 3)
+    perm = 4 * (row * width + col) + smp
+    inv = np.empty_like(perm)
+    inv[perm] = k
+    return perm, inv
+
+
+def camera_rays(frame, order="pixel"):
+    """The 4 W H camera rays of `frame` as (origins, dirs), (n, 3) float32 each,
+    bit for bit what rt_hip_frame_rays writes: the float arithmetic of
+    cpu/raytracer.c:55-60 (csrc/rt_render.hip camera_ray) -- sample s of PPM
+    pixel (row, col) has k = i + 0.5 (s >> 1), l = j + 0.5 (s & 1) with
+    i = W - col - W/2, j = H - row - H/2, its origin (C + u k) + v l on the
+    film and its direction normalize(position - origin).  order: "pixel" (ray
+    4 (row W + col) + s) or "quarter" (quarter_order)."""
+    W, H = int(frame.width), int(frame.height)
+    f32 = np.float32
+    idx = np.arange(4 * W * H, dtype=np.int64)
+    if RAY_ORDER[order] if isinstance(order, str) else order:
+        idx = quarter_order(W, H)[0]
+    px, smp = idx >> 2, idx & 3
+    row, col = px // W, px % W
+    k = (W - col - W // 2).astype(f32) + f32(0.5) * (smp >> 1).astype(f32)
+    l = (H - row - H // 2).astype(f32) + f32(0.5) * (smp & 1).astype(f32)
+
+    def v3(v):
+        return [f32(v.x), f32(v.y), f32(v.z)]
+    u, v, c, pos = v3(frame.u), v3(frame.v), v3(frame.C), v3(frame.position)
+    o = [(c[a] + k * u[a]) + l * v[a] for a in range(3)]
+    d = [pos[a] - o[a] for a in range(3)]
+    s = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]  # float sum, f64 sqrt rounded to float (vector3_length)
+    ln = np.sqrt(s.astype(np.float64)).astype(f32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = [x / ln for x in d]
+    return np.stack(o, axis=1).astype(f32), np.stack(d, axis=1).astype(f32)
+
+
+def fold_samples(rgb):
+    """Pixels from sample colours: every 4 consecutive rows of rgb ((4 n, 3)
+    float32, a pixel's samples in cpu order) give acc = color_add(acc,
+    color_mul(s, 0.25)) from acc = 0 (cpu/raytracer.c:55-68, cpu/colors.c) in
+    float32 -> (n, 3)."""
+    f32 = np.float32
+    s = np.ascontiguousarray(rgb, dtype=f32).reshape(-1, 4, 3)
+    acc = np.zeros((len(s), 3), f32)
+    for j in range(4):
+        y = (s[:, j] / f32(255.0) * f32(0.25)) * f32(255.0)  # color_mul -> init_color
+        y = np.where(y > f32(255.0), f32(255.0), y)
+        y = np.where(y < f32(0.0), f32(0.0), y)
+        acc = acc + y  # color_add
+        acc = np.where(acc > f32(255.0), f32(255.0), acc)
+    return acc.astype(f32)
+
+
+def equirect_rays(position, width, height):
+    """An equirectangular panorama's rays from `position`: pixel (row, col)
+    looks along longitude 2 pi (col + 0.5) / width - pi (0 = +x, towards +z)
+    and latitude pi / 2 - pi (row + 0.5) / height (+y up), unit directions.
+    Host numpy only -> (origins, dirs), (width * height, 3) float32 each, row-major."""
+    rows, cols = np.mgrid[0:height, 0:width]
+    lon = 2.0 * np.pi * (cols + 0.5) / width - np.pi
+    lat = 0.5 * np.pi - np.pi * (rows + 0.5) / height
+    d = np.stack([np.cos(lat) * np.cos(lon), np.sin(lat), np.cos(lat) * np.sin(lon)], axis=-1)
+    d = (d / np.linalg.norm(d, axis=-1, keepdims=True)).reshape(-1, 3).astype(np.float32)
+    o = np.broadcast_to(np.asarray(position, np.float32), d.shape).copy()
+    return o, d
+
+
+def ortho_rays(position, u, v, extent, width, height):
+    """An orthographic view's rays: a width x height grid of parallel rays
+    along normalize(u x v), their origins on the plane through `position`
+    spanned by the unit vectors of u (to the right) and v (up), the grid
+    `extent` wide and extent * height / width high, pixel centres, row 0 on
+    top.  Host numpy only -> (origins, dirs), (width * height, 3) float32 each."""
+    u = np.asarray(u, np.float64) / np.linalg.norm(u)
+    v = np.asarray(v, np.float64) / np.linalg.norm(v)
+    w = np.cross(u, v)
+    w /= np.linalg.norm(w)
+    rows, cols = np.mgrid[0:height, 0:width]
+    x = ((cols + 0.5) / width - 0.5) * extent
+    y = (0.5 - (rows + 0.5) / height) * extent * height / width
+    o = np.asarray(position, np.float64) + x[..., None] * u + y[..., None] * v
+    o = o.reshape(-1, 3).astype(np.float32)
+    d = np.broadcast_to(w.astype(np.float32), o.shape).copy()
+    return o, d
 
 
 class Context:
@@ -810,6 +920,51 @@ class Context:
                                                              smp.ctypes.data_as(C.c_void_p), C.byref(st)),
                            "rt_hip_render_image_gbuffer")
         return img, smp, st.as_dict()
+
+    def _keep_rc(self, rc):
+        self.last_rc = rc
+        return rc
+
+    def trace_rays_device(self, d_origins, d_dirs, n, d_rgb=0, d_samples=0, packet=False, stream=None):
+        """rt_hip_trace_rays on device pointers (asynchronous): d_rgb receives
+        3 n floats, d_samples n GSAMPLE records; 0 leaves either out (d_rgb
+        = 0: a ray cast)."""
+        _check(lib().rt_hip_trace_rays(self.h, C.c_void_p(d_origins), C.c_void_p(d_dirs), int(n),
+                                       RT_RAYS_PACKET if packet else 0, C.c_void_p(d_rgb) if d_rgb else None,
+                                       C.c_void_p(d_samples) if d_samples else None,
+                                       C.c_void_p(stream) if stream else None), "rt_hip_trace_rays")
+
+    def trace_rays(self, origins, dirs, packet=False, samples=False, shade=True):
+        """trace(ray, 1.0) of cpu/raytracer.c:19-34 for (n, 3) float32 rays
+        (rt_hip_trace_rays_host; directions used as given) -> (rgb (n, 3)
+        float32 or None, GSAMPLE records (n,) of the first hits or None,
+        stats).  shade=False: a ray cast (samples only, one query per ray).
+        packet: each aligned 64 rays walk their first query as one packet --
+        the same bits, faster for coherent groups."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        assert len(o) == len(d)
+        samples = samples or not shade
+        rgb = np.zeros((len(o), 3), np.float32) if shade else None
+        smp = np.zeros(len(o), GSAMPLE) if samples else None
+        st = Stats()
+        self.last_rc = 0  # the call's return code (RT_EINEXACT passes _check_render after a parity-breaking knob)
+        self._check_render(self._keep_rc(lib().rt_hip_trace_rays_host(
+            self.h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), len(o),
+            RT_RAYS_PACKET if packet else 0, rgb.ctypes.data_as(C.c_void_p) if shade else None,
+            smp.ctypes.data_as(C.c_void_p) if samples else None, C.byref(st))), "rt_hip_trace_rays_host")
+        return rgb, smp, st.as_dict()
+
+    def frame_rays(self, frame, order="pixel"):
+        """The frame's 4 W H camera rays from the device generator
+        (rt_hip_frame_rays) -> (origins, dirs), (n, 3) float32 each; order
+        "pixel" or "quarter" (camera_rays is the numpy restatement)."""
+        n = 4 * frame.width * frame.height
+        o, d = np.empty((max(n, 0), 3), np.float32), np.empty((max(n, 0), 3), np.float32)
+        _check(lib().rt_hip_frame_rays_host(self.h, C.byref(frame), RAY_ORDER[order] if isinstance(order, str) else order,
+                                            o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)),
+               "rt_hip_frame_rays")
+        return o, d
 
     def render_compat(self, camera):
         """gpu/rt compatibility mode (rt_hip_render_compat) -> (H, W, 4)
