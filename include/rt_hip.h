@@ -436,6 +436,55 @@ int rt_hip_frame_rays(rt_hip_ctx *ctx, const rt_frame *frame, int order,
 int rt_hip_frame_rays_host(rt_hip_ctx *ctx, const rt_frame *frame, int order,
                            float *h_origins, float *h_dirs);
 
+/* Occlusion batches (new): "is anything in the way, up to this far?" for rays
+ * the caller supplies -- ambient occlusion, visibility between two points,
+ * light baking, line of sight.  The any-hit query behind the reference's
+ * has_direct_hit (cpu/light.c:24-31), with a distance bound.  Ray i is
+ * (d_origins[3i..], d_dirs[3i..]) as for rt_hip_trace_rays, the direction used
+ * as given; with D = collide_dist(scene, ray_i) of cpu/hit.c:93-109 (the least
+ * new_dist > 0.01 over the triangles ray_intersect accepts, 0 if none),
+ *
+ *     d_occluded[i] = (D != 0 && D <= d_tmax[i])     float compare
+ *
+ * d_tmax[i] is a world distance |hit point - origin| in the units of new_dist,
+ * not the Moller-Trumbore parameter: it does not scale with |d|.  d_tmax ==
+ * NULL means +inf for every ray, i.e. has_direct_hit.  A ray rt_hip_trace_rays
+ * would not trace (a non-finite component, an all-zero direction) and a ray
+ * whose tmax is NaN are not traced: byte 0.  A traced ray with tmax <= 0
+ * answers 0 without a query.  One byte per ray; bytes past n are never
+ * written.  n == 0 returns RT_OK and writes nothing; n > RT_RAYS_MAX, a NULL
+ * ray or output pointer, a non-default traversal policy or
+ * rt_hip_set_count_work: RT_EINVAL with nothing changed.  Asynchronous on
+ * `stream`, with rt_hip_render's threading rules.
+ *
+ * The answer is the same on every path: brute force over every record on a
+ * FLAT context; on octree contexts a per-lane any-hit walk at the culling slack
+ * that skips a node only when the ray misses its slack-grown box or the
+ * closest walk's prune rule puts it beyond tmax (tested against brute force,
+ * not proven, as a reflection ray's query; the plain slack boxes, not the
+ * shadow rays' proof, which is about the scene's lights); under
+ * rt_hip_set_exact_reflections the proven closest walk, answering dist <= tmax
+ * -- proven for |d| <= 1.0625, a longer direction is counted in
+ * closest_unproven and rt_hip_stats returns RT_EINEXACT, as for a ray batch.
+ * With RT_RAYS_PACKET each aligned group of 64 rays walks as one packet: the
+ * same bytes, faster for coherent groups; ignored on FLAT and under exact
+ * reflections.  A hit on an object whose interpolated normal can vanish is
+ * counted in shadow_zero_risk (RT_EZERONORMAL), never silent.
+ *
+ * A batch writes no hit record, so the kept frame survives it: rt_hip_relight,
+ * rt_hip_gbuffer and a streaming caller's next frame behave as if the batch had
+ * not happened.  rt_hip_stats directly after a batch describes the batch --
+ * camera = rays traced, shadow = traced rays with tmax > 0 (the queries),
+ * depth_overflow, shadow_zero_risk and closest_unproven as counted, every other
+ * counter 0 -- and after a later relight what it would have read without the
+ * batch.  rt_hip_frame_check counts renders only, as for a relight. */
+int rt_hip_occluded(rt_hip_ctx *ctx, const float *d_origins, const float *d_dirs, const float *d_tmax,
+                    size_t n, unsigned flags, unsigned char *d_occluded, void *stream);
+/* Upload, rt_hip_occluded on the context's stream, download, rt_hip_stats;
+ * synchronous. */
+int rt_hip_occluded_host(rt_hip_ctx *ctx, const float *h_origins, const float *h_dirs, const float *h_tmax,
+                         size_t n, unsigned flags, unsigned char *h_occluded, rt_stats *stats);
+
 /* gpu/rt compatibility mode (gpu/raytracer.cu:31-129,
  * gpu/light.cu, gpu/colors.cu): the camera's frame rendered at 3x width and
  * height with one ray per high-resolution pixel, uint8 saturating colours,

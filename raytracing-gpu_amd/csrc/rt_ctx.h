@@ -10,6 +10,7 @@
 //   rt_verify.cpp  probes, verification, timing and measurement hooks
 //   rt_multi.cpp   rt_raytrace_multi: N GPUs, RCCL exchange and gather
 //   rt_rays.cpp    rt_hip_trace_rays, rt_hip_frame_rays: a caller's ray batches
+//   rt_occl.cpp    rt_hip_occluded: a caller's occlusion batches
 // Internal, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -170,6 +171,15 @@ struct rt_hip_ctx {
   int lb_proven = -1;               // built proven (exact_shadows) or slack-grown
   unsigned long long lb_entry_cap = 0;  // test hook: fail builds past this many entries (0: none)
   int last_batch = 0;               // the last launch was a ray batch (rt_hip_trace_rays): rt_hip_stats reports rays, no list
+  // occlusion batches (rt_hip_occluded, csrc/rt_occl.cpp) count into a stats
+  // block of their own (the layout of d_stats): the render's trace-side
+  // counters, which a relight keeps, stay as they are.  last_occl: the last
+  // operation was such a batch, on occl_stream -- rt_hip_stats reads this
+  // block then; every render, relight, ray batch and compat render clears it
+  DevBuf<unsigned long long> d_occl_stats;
+  int occl_grid = 0;                // the kernel's persistent grid (0: not asked yet)
+  int last_occl = 0;
+  hipStream_t occl_stream = nullptr;
   KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here
   // exact shadow rays (csrc/rt_shadow.hip), built for the slack sh_ulps
   DevBuf<float2> d_prim_mu;
@@ -348,4 +358,5 @@ int choose_accel(const rt_scene* s);                                            
 int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, int compat = 0,
                  bool from_render = false);  // rt_lists.cpp
 unsigned long long* cost_sum_of(rt_hip_ctx* c);                                    // rt_lists.cpp
+int occl_stats(rt_hip_ctx* c, rt_stats* out);                                      // rt_occl.cpp
 

@@ -599,6 +599,7 @@ static void render_frame_params(KParams& p, const rt_hip_ctx* c, const rt_frame*
 static int render_done(rt_hip_ctx* c, const KParams& p, const rt_frame* f, hipStream_t s, int first_ev) {
   c->last_p = p;
   c->last_batch = 0;
+  c->last_occl = 0;
   if (c->gbuffer) {  // (an empty rank's rt_hip_gbuffer writes nothing either)
     c->gb_frame = *f;
     c->gb_valid = 1;
@@ -868,6 +869,9 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
 extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   if (!c || !out) return rt_set_error(RT_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(c->device));
+  // an occlusion batch counted into its own block and touched nothing a
+  // frame's readers use (csrc/rt_occl.cpp)
+  if (c->last_occl) return occl_stats(c, out);
   unsigned long long hs[RT_STAT_SETS * RT_STAT_STRIDE], h[RT_NSTATS];
   uint32_t hc[RT_HIT_REGIONS * RT_HIT_STRIDE];
   hipStream_t s = c->last_stream ? c->last_stream : c->stream;
@@ -1147,7 +1151,10 @@ extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
   if (c->policy != RT_POLICY_DEFAULT)
     return rt_set_error(RT_EINVAL, "a relight needs the default traversal policy (have %d)", c->policy);
   if (c->count_work) return rt_set_error(RT_EINVAL, "a relight cannot run as the work-counting pass");
-  if (lp.ntiles_local == 0) return RT_OK;  // a rank past the last block: nothing rendered, nothing written
+  if (lp.ntiles_local == 0) {  // a rank past the last block: nothing rendered, nothing written
+    c->last_occl = 0;
+    return RT_OK;
+  }
   HIP_TRY(hipSetDevice(c->device));
   // the render's parameters with the scene as it is now and nothing of the
   // render's shadow set-up (rebuilt below for the current lights and mode)
@@ -1204,6 +1211,7 @@ extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
   HIP_TRY(rt_launch_shade_fixup(&p, c->nprim, s));
   HIP_TRY(rt_launch_fold(&p, s));
   c->relight.masks_written();
+  c->last_occl = 0;
   c->last_p = p;  // rt_hip_stats (the deferred count), rt_hip_verify_shadows, rt_hip_gbuffer (its fields are the render's)
   return RT_OK;
 }
@@ -1370,6 +1378,7 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   }
   c->cost_hist.valid = 0;  // the counters are the compat render's
   c->last_batch = 0;
+  c->last_occl = 0;
   c->rl_valid = 0;         // (and no hit records are kept: nothing to relight)
   c->relight.invalidate();
   if (hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s) != hipSuccess ||

@@ -229,6 +229,19 @@ struct RayArgs {
   uint32_t* samples;     // RT_GB_WORDS_D words per ray (NULL: none)
 };
 
+// What an occlusion batch's kernel takes beside the KParams (csrc/rt_occl.h).
+// walk: RT_RAYS_WALK_PACKET (every aligned 64 rays as one packet) or
+// RT_RAYS_WALK_EXACT (the proven closest walk), else the per-lane bounded walk.
+struct OcclArgs {
+  const float* org;      // 3 floats per ray
+  const float* dir;      // 3 floats per ray, used as given
+  const float* tmax;     // one per ray, world distance (NULL: +inf for every ray)
+  unsigned long long n;  // rays
+  uint32_t nitems;       // rt_ray_item_count(n)
+  uint32_t walk;         // RT_RAYS_WALK_*
+  unsigned char* out;    // one byte per ray
+};
+
 // The three launches of one render (policy = RT_POLICY_*, octree only):
 // trace (closest hits -> hit records), shade (shadow queries + Phong per
 // record -> terms), fold (terms -> the rank's tile buffer)
@@ -276,6 +289,10 @@ extern "C" hipError_t rt_launch_rays_samples(const KParams* p, const RayArgs* a,
 // rt_hip_frame_rays: the 4 W H camera rays of p's frame (p->u, v, C, pos, W, H)
 // in pixel order (order 0) or quarter order (1), csrc/rt_ray_items.h
 extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* org, float* dir, hipStream_t stream);
+// An occlusion batch (csrc/rt_occl.h): its one kernel, one-wave workgroups
+// pulling items of 64 rays, and that kernel's persistent grid on `cus` CUs
+extern "C" hipError_t rt_launch_occl(const KParams* p, const OcclArgs* a, int accel, int grid, hipStream_t stream);
+extern "C" hipError_t rt_occl_grid(int accel, int cus, int* grid);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

@@ -92,6 +92,7 @@ extern "C" int rt_hip_trace_rays(rt_hip_ctx* c, const float* d_origins, const fl
   // history of the frames around the batch is touched
   c->last_p = p;
   c->last_batch = 1;
+  c->last_occl = 0;
   c->last_stream = s;
   return RT_OK;
 }

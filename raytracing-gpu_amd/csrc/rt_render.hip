@@ -771,6 +771,7 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
 #include "rt_recolour.h"  // relight_zero_kernel, recolour_kernel: after every render kernel
 #include "rt_shade_tables.h"  // shade_tables_kernel: after those
 #include "rt_rays.h"  // the ray batches' kernels: after those
+#include "rt_occl.h"  // the occlusion batches' kernel: last
 
 // ---------------------------------------------------------------- launchers
 // One instantiation per (kernel, accel, work counting, policy); the default
@@ -1007,4 +1008,27 @@ extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* o
   if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
   hipLaunchKernelGGL((rt::frame_rays_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *p, order, org, dir);
   return hipGetLastError();
+}
+
+// An occlusion batch's launch (rt_kernels.h, csrc/rt_occl.h).  Last, for the
+// same reason again: every earlier kernel keeps its place.
+static const void* occl_kernel_of(int accel) {
+  return accel == RT_ACCEL_FLAT_D ? (const void*)rt::rays_occl_kernel<RT_ACCEL_FLAT_D>
+                                  : (const void*)rt::rays_occl_kernel<RT_ACCEL_OCTREE_D>;
+}
+
+extern "C" hipError_t rt_occl_grid(int accel, int cus, int* grid) {
+  int per_cu = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, occl_kernel_of(accel), 64, 0);
+  if (e != hipSuccess) return e;
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 32) per_cu = 32;
+  *grid = per_cu * cus;
+  return hipSuccess;
+}
+
+extern "C" hipError_t rt_launch_occl(const KParams* p, const OcclArgs* a, int accel, int grid, hipStream_t stream) {
+  if (grid <= 0) return hipErrorInvalidValue;
+  void* args[] = {(void*)p, (void*)a};
+  return hipLaunchKernel(occl_kernel_of(accel), dim3(grid), dim3(64), args, 0, stream);
 }

@@ -220,6 +220,10 @@ _PROTOS = [
                                          C.c_void_p, C.POINTER(Stats)]),
     ("rt_hip_frame_rays", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_frame_rays_host", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_void_p, C.c_void_p]),
+    ("rt_hip_occluded", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p,
+                                  C.c_void_p]),
+    ("rt_hip_occluded_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint,
+                                       C.c_void_p, C.POINTER(Stats)]),
     ("rt_hip_malloc", C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("rt_hip_free", C.c_int, [C.c_void_p]),
     ("rt_hip_memcpy_d2h", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -605,6 +609,36 @@ def ortho_rays(position, u, v, extent, width, height):
     return o, d
 
 
+def hemisphere_rays(P, N, k, seed):
+    """Ambient-occlusion rays from a G-buffer: k cosine-weighted directions
+    about the normal of every surface point, origins at the points.  P, N:
+    (m, 3) points and normals (any length; a zero normal gets +z).  Host numpy
+    only, seeded -> (origins, dirs), (m k, 3) float32 each, a point's k rays
+    consecutive; the directions have unit length and dot(dir, N) > 0."""
+    P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1, 3)
+    n = np.ascontiguousarray(N, dtype=np.float64).reshape(-1, 3).copy()
+    assert len(P) == len(n) and k >= 1
+    ln = np.linalg.norm(n, axis=1)
+    n[ln == 0] = (0.0, 0.0, 1.0)
+    n /= np.where(ln == 0, 1.0, ln)[:, None]
+    # an orthonormal frame (t, b, n): t from the axis n leans on least
+    ax = np.eye(3)[np.argmin(np.abs(n), axis=1)]
+    t = np.cross(ax, n)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(n, t)
+    rng = np.random.default_rng(seed)
+    # cosine-weighted: a uniform point of the unit disc, lifted; the radius is
+    # kept off 1 so that the lifted direction stays clear of the tangent plane
+    r = np.sqrt(rng.random((len(P), k))) * 0.999
+    phi = 2.0 * np.pi * rng.random((len(P), k))
+    x, y = r * np.cos(phi), r * np.sin(phi)
+    z = np.sqrt(1.0 - r * r)
+    d = x[..., None] * t[:, None] + y[..., None] * b[:, None] + z[..., None] * n[:, None]
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    o = np.repeat(P, k, axis=0)
+    return o.astype(np.float32), d.reshape(-1, 3).astype(np.float32)
+
+
 class Context:
     """One device image of a scene (rt_hip_create); renders through the C ABI."""
 
@@ -965,6 +999,37 @@ class Context:
                                             o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p)),
                "rt_hip_frame_rays")
         return o, d
+
+    def occluded_device(self, d_origins, d_dirs, d_tmax, n, d_out, packet=False, stream=None):
+        """rt_hip_occluded on device pointers (asynchronous): d_out receives n
+        bytes, 1 where something lies within d_tmax[i] (world distance) along
+        ray i; d_tmax = 0 (NULL): no bound."""
+        _check(lib().rt_hip_occluded(self.h, C.c_void_p(d_origins) if d_origins else None,
+                                     C.c_void_p(d_dirs) if d_dirs else None, C.c_void_p(d_tmax) if d_tmax else None,
+                                     int(n), RT_RAYS_PACKET if packet else 0, C.c_void_p(d_out) if d_out else None,
+                                     C.c_void_p(stream) if stream else None), "rt_hip_occluded")
+
+    def occluded(self, origins, dirs, tmax=None, packet=False):
+        """Is anything in the way of (n, 3) float32 rays, up to tmax
+        (rt_hip_occluded_host)?  byte i = collide_dist(ray i) != 0 and <=
+        tmax[i] (cpu/hit.c:93-109); tmax: None (no bound: has_direct_hit), a
+        scalar or (n,) world distances, independent of |dir| -> (uint8 (n,),
+        stats).  packet: each aligned 64 rays walk as one packet -- the same
+        bytes, faster for coherent groups."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        assert len(o) == len(d)
+        t = None
+        if tmax is not None:
+            t = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (len(o),)))
+        out = np.zeros(len(o), np.uint8)
+        st = Stats()
+        self.last_rc = 0  # the call's return code (RT_EINEXACT passes _check_render after a parity-breaking knob)
+        self._check_render(self._keep_rc(lib().rt_hip_occluded_host(
+            self.h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+            t.ctypes.data_as(C.c_void_p) if t is not None else None, len(o), RT_RAYS_PACKET if packet else 0,
+            out.ctypes.data_as(C.c_void_p), C.byref(st))), "rt_hip_occluded_host")
+        return out, st.as_dict()
 
     def render_compat(self, camera):
         """gpu/rt compatibility mode (rt_hip_render_compat) -> (H, W, 4)
