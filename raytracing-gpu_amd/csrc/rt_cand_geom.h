@@ -111,6 +111,12 @@ RTC_FN int classify(const CandParams& p, const float* r, const float* leafbox, F
     if (why) *why = 0;
     return SAFE;
   }
+  // degenerate (collinear or repeated vertices) with edges long enough for
+  // rounding alone to lift |a| past 1e-7: a is noise, u and v are unbounded,
+  // no line has a bound (c_ok = inf) and n / |n| would put NaN into every band
+  // coefficient below -- every camera ray tests it (as rt_lightbuf_geom.h's
+  // footprint_point_proven does for the shadow rays)
+  if (!(nl > 0.0)) return GLOBAL;
   const double inl = 1.0 / nl;  // (the unit normal to an ulp or two: inside every margin below)
   const double nh[3] = {n[0] * inl, n[1] * inl, n[2] * inl};
   const double pv[3] = {p.pos[0] - v0[0], p.pos[1] - v0[1], p.pos[2] - v0[2]};
