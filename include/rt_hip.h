@@ -331,6 +331,68 @@ int rt_hip_relight(rt_hip_ctx *ctx, const rt_frame *frame, int rank, int nranks,
                    float *d_tiles, void *stream);
 int rt_hip_relight_image(rt_hip_ctx *ctx, const rt_frame *frame, float *h_rgb, rt_stats *stats);
 
+/* Moving geometry (new): new triangles in a live context, everything that
+ * depends on them rebuilt on the device.  An animated object, a simulated
+ * cloth or a skinned mesh needs no new rt_hip_create per frame: the caller's
+ * vertices -- a device tensor already, with PyTorch-ROCm as the plumbing --
+ * replace a range of the scene's triangles, and the device derives what
+ * rt_hip_create's host flatten derives (host/accel.c rt_flatten): the records'
+ * v0, e1 = v1 - v0, e2 = v2 - v0, the normalised vertex normals (the same IEEE
+ * sqrt and quotients as the host's), the scene's bounding box over every
+ * triangle (a partial update can shrink it) and each touched object's
+ * zero-normal risk flag from all of its triangles (csrc/rt_geom.hip).
+ *
+ * rt_hip_set_triangles replaces the triangles [first, first + count) of the
+ * scene, in prim order (object, then the object's triangle index: the order of
+ * rt_gsample.prim), by `count` records of rt_triangle layout (18 floats:
+ * vertex[3], normal[3]) read from d_triangles, device memory of the context's
+ * device, on the context's stream.  rt_hip_set_triangles_host uploads them
+ * first.  The topology stays as created: the objects, their triangle counts
+ * and the prim numbering do not change.  Values are taken as rt_hip_create
+ * takes the scene's: no validation, a non-finite vertex is as undefined as it
+ * is there.
+ *
+ * Synchronous setup, like rt_hip_set_lights: it waits for the context's last
+ * stream and for the side stream, and returns when everything is rebuilt, in
+ * rt_hip_create's order -- the octree (RT_ACCEL_OCTREE_GPU; a FLAT context's
+ * records are its scene image), the light buffers with create's fallbacks,
+ * the proven shadow walk's multipliers and the exact-reflection bounds where
+ * the context had built them.  rt_accel_info's build_seconds and
+ * lightbuf_seconds become those of the update.
+ *
+ * After RT_OK every later call on the context gives what the same call gives
+ * on a fresh context made by rt_hip_create on the edited scene with the same
+ * accel and brought to the same settings, bit for bit: images, G-buffer
+ * records, ray-batch colours and hit records, occlusion bytes, every rt_stats
+ * counter, every non-timing field of rt_accel_info, rt_hip_accel_validate.
+ * Buffer capacities are the only exceptions: the hit-record buffers keep
+ * their size and the list forecast starts over, so either side may answer a
+ * first frame with RT_EHITBUF where the other does not (render again, as
+ * rt_hip_render_image does).  The settings (exact shadows, exact reflections,
+ * G-buffer, keep-visibility, slacks, policy, overlap) and the lights and
+ * materials as last edited persist.  What described the old geometry is
+ * forgotten: the kept frame (rt_hip_relight and rt_hip_gbuffer return
+ * RT_EINVAL until the next rt_hip_render), consumed candidate lists, the list
+ * forecast, the item clocks, the last batch.
+ *
+ * RT_EINVAL, with nothing changed: a NULL context; a NULL pointer with
+ * count > 0; first + count past the context's triangle count; a context whose
+ * octree was built on the host (RT_ACCEL_OCTREE: its tree comes from the
+ * rt_scene -- make a new context or use RT_ACCEL_OCTREE_GPU).  count == 0 is
+ * RT_OK and a true no-op: nothing is invalidated, a kept frame still relights.
+ * A failure after the records were touched (RT_EHIP, out of memory in the tree
+ * or a buffer) leaves the context broken: every entry point that takes it,
+ * but rt_hip_set_triangles*, rt_hip_geometry_updates, rt_hip_accel_info and
+ * rt_hip_destroy, then returns RT_EINVAL with a message that says so; a later
+ * successful update heals it.
+ *
+ * Not here: refitting the tree without a rebuild, changing triangle counts,
+ * host-tree contexts, a transform API (the caller's tensor library does
+ * that), rt_raytrace_multi (it owns its contexts). */
+int rt_hip_set_triangles(rt_hip_ctx *ctx, const void *d_triangles, size_t first, size_t count);
+int rt_hip_set_triangles_host(rt_hip_ctx *ctx, const rt_triangle *h_triangles, size_t first, size_t count);
+int rt_hip_geometry_updates(const rt_hip_ctx *ctx, unsigned long long *n);   /* successful updates so far */
+
 /* Per-sample G-buffer (new; opt-in, default off): what the renderer knows
  * about each of a pixel's four camera samples beside its colour.  One record
  * of RT_GB_WORDS 32-bit words per sample, 4 per pixel in cpu sample order:

@@ -74,6 +74,11 @@ int rt_hip_set_camera_slack(rt_hip_ctx *ctx, float ulps);
  * more than the frame took. */
 int rt_hip_set_timing(rt_hip_ctx *ctx, int enable);
 int rt_hip_frame_times(rt_hip_ctx *ctx, int n, float *lists_ms, float *render_ms);
+/* The last successful rt_hip_set_triangles in wall seconds, each phase ended
+ * by a wait for the context's stream: [0] flatten + scene box + zero-normal
+ * flags, [1] the octree rebuild (0 on FLAT), [2] the light buffers (zeros
+ * before the first update; tools/geometry_cost.py). */
+int rt_hip_geometry_times(const rt_hip_ctx *ctx, double seconds[3]);
 /* The render span of the same frames split by kernel: trace (closest-hit
  * paths -> hit records), shade (shadow queries + Phong terms per record),
  * fold (terms -> tile buffer). */

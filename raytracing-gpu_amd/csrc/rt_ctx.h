@@ -31,6 +31,7 @@
 #include "rt_cand.h"
 #include "rt_kernels.h"
 #include "rt_forecast.h"
+#include "rt_geom.h"
 #include "rt_overlap.h"
 #include "rt_ray_items.h"
 #include "rt_lightbuf.h"
@@ -216,6 +217,20 @@ struct rt_hip_ctx {
   float4* d_tri_prim = nullptr;  // view: prim-order records, d_tri (FLAT) or d_tri_prim_own
   DevBuf<float4> d_tri_prim_own;
   uint32_t nprim = 0;
+  // geometry updates (rt_hip_set_triangles, csrc/rt_geom.hip).  accel says
+  // RT_ACCEL_OCTREE for both kinds of tree: dev_tree remembers that the device
+  // built this one (a host tree needs the rt_scene and is not rebuilt).
+  // broken: an update failed after it touched the records -- every entry
+  // point but the update, rt_hip_accel_info and rt_hip_destroy refuses until
+  // an update succeeds (ctx_live)
+  int dev_tree = 0;
+  int broken = 0;
+  unsigned long long geom_updates = 0;
+  std::vector<uint32_t> obj_start;  // nobj + 1: each object's first prim (the topology stays as created)
+  DevBuf<float> d_pbox;             // nprim x 6: each prim's vertex box (the scene box of a partial update)
+  DevBuf<uint32_t> d_objflag;       // nobj: the zero-normal risk flags, recomputed per update
+  DevBuf<float> d_geom_box;         // RT_GEOM_BOX_FLOATS: the scene-box reduction
+  double geom_seconds[3] = {};      // the last update's flatten + box + flags, tree, light buffers
   DevBuf<uint32_t> d_cand_list;    // nprim
   DevBuf<void> d_cand_fp;          // nprim footprints (rt_cand_footprint_bytes each)
   DevBuf<uint4> d_cand_sfp;        // 2 nprim: compact small footprints (CandParams::sfp)
@@ -292,6 +307,19 @@ struct rt_hip_ctx {
   }
 };
 
+// RT_OK for a context whose scene image is whole; RT_EINVAL (said so) after
+// a geometry update that failed half way (rt_hip_set_triangles)
+static inline int ctx_live(const rt_hip_ctx* c) {
+  if (c && c->broken)
+    return rt_set_error(RT_EINVAL, "the context is broken: a geometry update failed after it touched the records "
+                                   "(update again with rt_hip_set_triangles, or destroy it)");
+  return RT_OK;
+}
+#define RT_CTX_LIVE(c)                 \
+  do {                                 \
+    if (int live_ = ctx_live(c)) return live_; \
+  } while (0)
+
 // A setting that changes the lists (ListForecast::reset)
 static inline void lists_changed(rt_hip_ctx* c) {
   if (c->overlap.in_flight && c->side_stream.s) (void)hipStreamSynchronize(c->side_stream);
@@ -331,13 +359,17 @@ static inline KParams scene_params(const rt_hip_ctx* c) {
 // Centre and half extent (max-norm) of the scene's bounding box, in float:
 // what the culling slack is relative to (rt_hip_create keeps them in the
 // context; the host surveys derive the same values).  Zeros for an empty scene.
-static inline void scene_extent(const rt_flat_scene& fs, float c[3], float* r) {
+static inline void scene_extent(size_t ntri, const float scene_lo[3], const float scene_hi[3], float c[3],
+                                float* r) {
   *r = 0;
   for (int a = 0; a < 3; a++) {
-    float lo = fs.ntri ? fs.scene_lo[a] : 0.0f, hi = fs.ntri ? fs.scene_hi[a] : 0.0f;
+    float lo = ntri ? scene_lo[a] : 0.0f, hi = ntri ? scene_hi[a] : 0.0f;
     c[a] = 0.5f * (lo + hi);
     *r = std::fmax(*r, 0.5f * (hi - lo));
   }
+}
+static inline void scene_extent(const rt_flat_scene& fs, float c[3], float* r) {
+  scene_extent(fs.ntri, fs.scene_lo, fs.scene_hi, c, r);
 }
 
 // The kernels a render launches (render_kernels)

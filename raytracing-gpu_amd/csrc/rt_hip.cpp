@@ -59,12 +59,14 @@ extern "C" void rt_hip_destroy(rt_hip_ctx* c) {
 
 extern "C" int rt_hip_set_overlap_lists(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->overlap.set_enabled(enable != 0);
   return RT_OK;
 }
 
 extern "C" int rt_hip_overlap_builds(const rt_hip_ctx* c, unsigned long long* n) {
   if (!c || !n) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   *n = c->overlap.side_builds;
   return RT_OK;
 }
@@ -228,6 +230,7 @@ int lbuf_prepare(rt_hip_ctx* c, hipStream_t s) {
 
 extern "C" int rt_hip_set_light_buffers(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->light_buffers = enable ? 1 : 0;
   c->relight.invalidate();  // the kept masks were decided the other way
   if (!c->light_buffers) lbuf_release(c);
@@ -236,11 +239,73 @@ extern "C" int rt_hip_set_light_buffers(rt_hip_ctx* c, int enable) {
 
 extern "C" int rt_hip_set_lightbuf_entry_cap(rt_hip_ctx* c, unsigned long long cap) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->lb_entry_cap = cap;
   c->relight.invalidate();
   lbuf_release(c);  // rebuilt (and the cap applied) by the next render
   HIP_TRY(hipSetDevice(c->device));
   return lbuf_prepare(c, c->stream);
+}
+
+// ---- what rt_hip_create and rt_hip_set_triangles share: everything that
+// follows from the prim-order records and the scene box ----
+
+// The device-built octree of the prim-order records and the box in
+// scene_lo / scene_hi (contexts with dev_tree): the old tree and leaf-order
+// records go, the new ones are adopted with their counts.  Synchronises the
+// context's stream.
+static int tree_rebuild(rt_hip_ctx* c) {
+  c->d_tri.reset();
+  c->d_node.reset();
+  c->nrec = 0;
+  // leaf cap 24 measured best on C5 with the trace / shade / fold split and
+  // the candidate lists (12: 10.01-10.06 ms, 20 / 24: 9.89, 28: 9.99, 32: 10.01;
+  // profiles/r05u_leaf_sweep/); clip level 7 (6 / 8 no better)
+  rt_device_build_opts o{24, 7};
+  if (const char* e = std::getenv("RT_DEV_LEAF")) o.leaf_cap = std::atoi(e);  // tuning knobs
+  if (const char* e = std::getenv("RT_DEV_CLIP")) o.clip_level = std::atoi(e);
+  rt_device_tree tree{};
+  hipError_t he = rt_device_build_octree(c->d_tri_prim, c->nprim, c->scene_lo, c->scene_hi, &o, c->stream, &tree);
+  if (he != hipSuccess) return rt_set_error(RT_EHIP, "device octree build: %s", hipGetErrorString(he));
+  // leaf-order records for the walk; the prim-order ones stay for the
+  // camera candidate lists
+  c->d_tri.adopt(tree.tri, (size_t)tree.nref * RT_TRI_FLOATS / 4);
+  c->d_node.adopt(tree.node, (size_t)tree.nnode * RT_NODE_FLOATS / 4);
+  c->nrec = tree.nref;
+  c->info.nodes = tree.nnode;
+  c->info.leaves = tree.leaves;
+  c->info.max_depth = tree.depth;
+  c->info.max_leaf = tree.max_leaf;
+  return RT_OK;
+}
+
+// The scene's extent and rt_accel_info's sizes, from scene_lo / scene_hi,
+// nprim, nrec, the tree's counts and the tables as they stand.
+static void scene_publish(rt_hip_ctx* c) {
+  scene_extent(c->nprim, c->scene_lo, c->scene_hi, c->scene_c, &c->scene_r);
+  c->info.triangles = c->nprim;
+  c->info.tri_refs = c->nrec;
+  c->info.tri_record_bytes = RT_TRI_FLOATS * sizeof(float);
+  c->info.node_record_bytes = RT_NODE_FLOATS * sizeof(float);
+  c->info.device_bytes = ((size_t)c->nrec * RT_TRI_FLOATS + (size_t)c->nprim * 9 + c->mat_host.size() +
+                          (size_t)c->nlight * RT_LIGHT_FLOATS + (size_t)c->info.nodes * RT_NODE_FLOATS) *
+                         sizeof(float);
+  for (int a = 0; a < 3; a++) c->info.scene_center[a] = c->scene_c[a];
+  c->info.scene_radius = c->scene_r;
+}
+
+// Light buffers: part of the scene's setup, like the octree.  Built with the
+// buffers on, whatever the setting, so that rt_accel_info's totals describe
+// this geometry (rt_hip_set_light_buffers(0) releases buffers, never totals).
+static int scene_light_buffers(rt_hip_ctx* c) {
+  const auto l0 = std::chrono::steady_clock::now();
+  const int want = c->light_buffers;
+  c->light_buffers = 1;
+  const int rc = lbuf_prepare(c, c->stream);
+  c->light_buffers = want;
+  if (!rc && !want) lbuf_release(c);
+  c->info.lightbuf_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - l0).count();
+  return rc;
 }
 
 extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hip_ctx** out) {
@@ -294,37 +359,29 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
   }
   if (!rc && hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking) != hipSuccess)
     rc = rt_set_error(RT_EHIP, "hipStreamCreate");
-  rt_device_tree tree{};
-  if (!rc && dev_build && fs.ntri) {
-    // leaf cap 24 measured best on C5 with the trace / shade / fold split and
-    // the candidate lists (12: 10.01-10.06 ms, 20 / 24: 9.89, 28: 9.99, 32: 10.01;
-    // profiles/r05u_leaf_sweep/); clip level 7 (6 / 8 no better)
-    rt_device_build_opts o{24, 7};
-    if (const char* e = std::getenv("RT_DEV_LEAF")) o.leaf_cap = std::atoi(e);  // tuning knobs
-    if (const char* e = std::getenv("RT_DEV_CLIP")) o.clip_level = std::atoi(e);
-    hipError_t he = rt_device_build_octree(c->d_tri, (uint32_t)fs.ntri, fs.scene_lo, fs.scene_hi,
-                                           &o, c->stream, &tree);
-    if (he != hipSuccess) {
-      rc = rt_set_error(RT_EHIP, "device octree build: %s", hipGetErrorString(he));
-    } else {
-      // leaf-order records for the walk; the prim-order ones stay for the
-      // camera candidate lists
-      c->d_tri_prim_own = std::move(c->d_tri);
-      c->d_tri_prim = c->d_tri_prim_own;
-      c->d_tri.adopt(tree.tri, (size_t)tree.nref * RT_TRI_FLOATS / 4);
-      c->d_node.adopt(tree.node, (size_t)tree.nnode * RT_NODE_FLOATS / 4);
-      c->nrec = tree.nref;
-      bytes_tri = (size_t)tree.nref * RT_TRI_FLOATS * sizeof(float);
-      bytes_node = (size_t)tree.nnode * RT_NODE_FLOATS * sizeof(float);
-      fs.nrec = tree.nref;
-      fs.nnode = tree.nnode;
-      fs.leaves = tree.leaves;
-      fs.max_depth = tree.depth;
-      fs.max_leaf = tree.max_leaf;
-    }
+  c->nprim = (uint32_t)fs.ntri;
+  for (int a = 0; a < 3; a++) {
+    c->scene_lo[a] = fs.ntri ? fs.scene_lo[a] : 0.0f;
+    c->scene_hi[a] = fs.ntri ? fs.scene_hi[a] : 0.0f;
+  }
+  c->info.nodes = fs.nnode;  // (the host's tree, or none; a device tree brings its own)
+  c->info.leaves = fs.leaves;
+  c->info.max_depth = fs.max_depth;
+  c->info.max_leaf = fs.max_leaf;
+  c->dev_tree = dev_build && fs.ntri;
+  if (!rc && c->dev_tree) {
+    c->d_tri_prim_own = std::move(c->d_tri);
+    c->d_tri_prim = c->d_tri_prim_own;
+    rc = tree_rebuild(c);
   }
   auto t2 = std::chrono::steady_clock::now();
-  c->nprim = (uint32_t)fs.ntri;
+  // what a geometry update needs beside the records (rt_hip_set_triangles;
+  // a host tree is never updated): every prim's vertex box, each object's
+  // first prim
+  if (!rc && accel != RT_ACCEL_OCTREE) rc = upload(c->d_pbox, fs.pbox, fs.ntri * 6 * sizeof(float));
+  c->obj_start.assign(1, 0u);
+  for (size_t o = 0; o < scene->object_count; o++)
+    c->obj_start.push_back(c->obj_start.back() + scene->objects[o].triangle_count);
   if (!rc && !c->d_tri_prim) {
     if (c->accel == RT_ACCEL_FLAT) {
       c->d_tri_prim = c->d_tri;  // already prim order (no candidates needed)
@@ -338,22 +395,9 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
       }
     }
   }
-  scene_extent(fs, c->scene_c, &c->scene_r);
-  for (int a = 0; a < 3; a++) {
-    c->scene_lo[a] = fs.ntri ? fs.scene_lo[a] : 0.0f;
-    c->scene_hi[a] = fs.ntri ? fs.scene_hi[a] : 0.0f;
-  }
-  c->info.triangles = fs.ntri;
-  c->info.tri_refs = fs.nrec;
-  c->info.nodes = fs.nnode;
-  c->info.leaves = fs.leaves;
-  c->info.max_depth = fs.max_depth;
-  c->info.max_leaf = fs.max_leaf;
-  c->info.tri_record_bytes = RT_TRI_FLOATS * sizeof(float);
-  c->info.node_record_bytes = RT_NODE_FLOATS * sizeof(float);
-  c->info.device_bytes = bytes_tri + bytes_nrm + bytes_mat + bytes_light + bytes_node;
-  c->info.build_seconds = std::chrono::duration<double>(dev_build ? t2 - t0 : t1 - t0).count();
   if (fs.mat) c->mat_host.assign(fs.mat, fs.mat + fs.nobj * RT_MAT_FLOATS);
+  scene_publish(c);
+  c->info.build_seconds = std::chrono::duration<double>(dev_build ? t2 - t0 : t1 - t0).count();
   rt_flat_free(&fs);
   if (!rc) rc = shade_tables(c, true, true);
   if (rc) {
@@ -387,22 +431,16 @@ extern "C" int rt_hip_create(int device, const rt_scene* scene, int accel, rt_hi
       }
   c->info.trace_grid = c->grid_of[1][RT_POLICY_DEFAULT][0];
   c->info.shade_grid = c->grid_of[0][RT_POLICY_LBUF][0];
-  for (int a = 0; a < 3; a++) c->info.scene_center[a] = c->scene_c[a];
-  c->info.scene_radius = c->scene_r;
   // per-lane traversal stack spill area, [entry][lane] for the largest grid
   if (c->accel == RT_ACCEL_OCTREE &&
       c->d_spill.alloc((size_t)gmax * 64 * RT_SPILL_STACK) != hipSuccess) {
     rt_hip_destroy(c);
     return rt_set_error(RT_EHIP, "hipMalloc traversal spill stack");
   }
-  {  // light buffers: part of the scene's setup, like the octree
-    const auto l0 = std::chrono::steady_clock::now();
-    rc = lbuf_prepare(c, c->stream);
-    c->info.lightbuf_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - l0).count();
-    if (rc) {
-      rt_hip_destroy(c);
-      return rc;
-    }
+  rc = scene_light_buffers(c);
+  if (rc) {
+    rt_hip_destroy(c);
+    return rc;
   }
   *out = c;
   return RT_OK;
@@ -416,6 +454,7 @@ extern "C" int rt_hip_accel_info(const rt_hip_ctx* c, rt_accel_info* out) {
 
 extern "C" int rt_hip_set_cull_slack(rt_hip_ctx* c, float ulps) {
   if (!c || !(ulps >= 0.0f)) return rt_set_error(RT_EINVAL, "bad slack");
+  RT_CTX_LIVE(c);
   c->eps_ulps = ulps;
   c->cam_eps_ulps = ulps;
   c->relight.invalidate();
@@ -425,6 +464,7 @@ extern "C" int rt_hip_set_cull_slack(rt_hip_ctx* c, float ulps) {
 
 extern "C" int rt_hip_set_camera_slack(rt_hip_ctx* c, float ulps) {
   if (!c || !(ulps >= 0.0f)) return rt_set_error(RT_EINVAL, "bad slack");
+  RT_CTX_LIVE(c);
   c->cam_eps_ulps = ulps;
   lists_changed(c);  // the lists change
   return RT_OK;
@@ -432,12 +472,14 @@ extern "C" int rt_hip_set_camera_slack(rt_hip_ctx* c, float ulps) {
 
 extern "C" int rt_hip_set_exact_camera(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->exact_camera = enable ? 1 : 0;
   return RT_OK;
 }
 
 extern "C" int rt_hip_set_exact_shadows(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->exact_shadows = enable ? 1 : 0;
   c->relight.invalidate();
   // built now (setup), reported by rt_hip_accel_info: the light buffers in
@@ -485,6 +527,7 @@ int reflect_prepare(rt_hip_ctx* c, hipStream_t s) {
 
 extern "C" int rt_hip_set_exact_reflections(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->exact_refl = enable ? 1 : 0;
   if (!c->exact_refl) return RT_OK;
   HIP_TRY(hipSetDevice(c->device));
@@ -493,6 +536,7 @@ extern "C" int rt_hip_set_exact_reflections(rt_hip_ctx* c, int enable) {
 
 extern "C" int rt_hip_set_policy(rt_hip_ctx* c, int policy) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   if (policy < RT_POLICY_DEFAULT || policy > RT_POLICY_DIR_STAGED)
     return rt_set_error(RT_EINVAL, "unknown traversal policy %d", policy);
   c->policy = policy;
@@ -502,6 +546,7 @@ extern "C" int rt_hip_set_policy(rt_hip_ctx* c, int policy) {
 
 extern "C" int rt_hip_set_camera_refine(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->cand_refine = enable ? 1 : 0;
   lists_changed(c);  // the lists change
   return RT_OK;
@@ -509,6 +554,7 @@ extern "C" int rt_hip_set_camera_refine(rt_hip_ctx* c, int enable) {
 
 extern "C" int rt_hip_set_camera_bound_scale(rt_hip_ctx* c, double scale) {
   if (!c || !(scale > 0.0)) return rt_set_error(RT_EINVAL, "bad bound scale");
+  RT_CTX_LIVE(c);
   c->bound_scale = scale;
   lists_changed(c);  // the lists change
   return RT_OK;
@@ -555,6 +601,7 @@ int hit_buffers(rt_hip_ctx* c, size_t items, bool capture) {
 // The refusals: nothing of the context has changed when one of them returns.
 static int render_refuse(const rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, const float* d_tiles) {
   if (!c || !f || !d_tiles) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (nranks <= 0 || rank < 0 || rank >= nranks)
     return rt_set_error(RT_EINVAL, "rank %d of %d", rank, nranks);
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
@@ -868,6 +915,7 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
 
 extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   if (!c || !out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   HIP_TRY(hipSetDevice(c->device));
   // an occlusion batch counted into its own block and touched nothing a
   // frame's readers use (csrc/rt_occl.cpp)
@@ -973,6 +1021,7 @@ extern "C" int rt_hip_assemble(rt_hip_ctx* c, const rt_frame* f, const float* d_
                                int nranks, float* d_rgb, void* stream) {
   if (!c || !f || !d_gathered || !d_rgb || nranks <= 0)
     return rt_set_error(RT_EINVAL, "bad argument");
+  RT_CTX_LIVE(c);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   int tx = tiles_x_of(f->width);
@@ -984,6 +1033,7 @@ extern "C" int rt_hip_assemble(rt_hip_ctx* c, const rt_frame* f, const float* d_
 
 extern "C" int rt_hip_render_image(rt_hip_ctx* c, const rt_frame* f, float* h_rgb, rt_stats* st) {
   if (!c || !f || !h_rgb) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   HIP_TRY(hipSetDevice(c->device));
   size_t nt = rt_hip_tile_buffer_floats(f->width, f->height, 1);
   size_t npx = (size_t)f->width * f->height;
@@ -1025,6 +1075,7 @@ static int relight_quiesce(rt_hip_ctx* c) {
 
 extern "C" int rt_hip_set_lights(rt_hip_ctx* c, const rt_light* lights, size_t n) {
   if (!c || (n && !lights)) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (n > 0x7fffffffu / RT_LIGHT_FLOATS) return rt_set_error(RT_EINVAL, "%zu lights", n);
   HIP_TRY(hipSetDevice(c->device));
   int rc = relight_quiesce(c);
@@ -1102,6 +1153,7 @@ extern "C" int rt_hip_set_lights(rt_hip_ctx* c, const rt_light* lights, size_t n
 
 extern "C" int rt_hip_set_materials(rt_hip_ctx* c, const rt_object* objects, size_t n) {
   if (!c || (n && !objects)) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (n * RT_MAT_FLOATS != c->mat_host.size())
     return rt_set_error(RT_EINVAL, "%zu objects, the context has %zu", n, c->mat_host.size() / RT_MAT_FLOATS);
   std::vector<float> rows(c->mat_host.size(), 0.0f);
@@ -1130,8 +1182,148 @@ extern "C" int rt_hip_set_materials(rt_hip_ctx* c, const rt_object* objects, siz
   return tables;
 }
 
+// --------------------------------------------------------- moving geometry
+// New triangles in a live context (include/rt_hip.h rt_hip_set_triangles):
+// the device derives what rt_flatten derives (csrc/rt_geom.hip), then
+// everything keyed on the geometry is rebuilt in rt_hip_create's order and
+// everything that described the old geometry is forgotten.
+
+// Nothing of the old geometry's frames, lists or batches is current.
+static int geometry_forget(rt_hip_ctx* c) {
+  lists_changed(c);  // joins a side-stream build; the forecast and pknown start over
+  c->overlap.lists_touched();
+  c->ext_ready = 0;
+  c->cost_hist.valid = 0;
+  c->rl_valid = 0;
+  c->gb_valid = 0;
+  c->relight.invalidate();
+  c->last_batch = 0;
+  c->last_occl = 0;
+  c->last_async = 0;
+  c->d_cand_valid = nullptr;
+  c->list_flag = nullptr;
+  c->cand_prims = c->cand_entries = c->cand_global = 0;
+  c->send_n = 0;
+  std::memset(&c->last_p, 0, sizeof c->last_p);  // its views pointed into the old records and nodes
+  std::memset(&c->ext, 0, sizeof c->ext);
+  HIP_TRY(hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, c->stream));  // no frame's counters either
+  return RT_OK;
+}
+
+// d_src: count (> 0) records in device memory; the range is inside the
+// context's prims.  Leaves the context broken on failure.
+static int geometry_update(rt_hip_ctx* c, const float* d_src, size_t first, size_t count) {
+  using clk = std::chrono::steady_clock;
+  const auto secs = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+  HIP_TRY(hipSetDevice(c->device));
+  int rc = relight_quiesce(c);
+  if (rc) return rc;
+  if (c->occl_stream && c->occl_stream != c->stream.s) HIP_TRY(hipStreamSynchronize(c->occl_stream));
+  c->broken = 1;
+  if ((rc = geometry_forget(c))) return rc;
+  hipStream_t s = c->stream;
+  const size_t nobj = c->obj_start.size() - 1;
+  if (!c->d_pbox.holds((size_t)c->nprim * 6)) return rt_set_error(RT_EHIP, "geometry update: the prims' boxes are missing");
+  if (!c->d_objflag.holds(nobj)) HIP_TRY(c->d_objflag.alloc(nobj));
+  if (!c->d_geom_box.holds(RT_GEOM_BOX_FLOATS)) HIP_TRY(c->d_geom_box.alloc(RT_GEOM_BOX_FLOATS));
+  const auto t0 = clk::now();
+  // 1: the range's records, normal rows and vertex boxes
+  HIP_TRY(rt_geom_flatten(d_src, (uint32_t)first, (uint32_t)count, c->d_tri_prim, c->d_nrm, c->d_pbox, s));
+  // 2: the scene box, over every prim (a partial update can shrink it)
+  HIP_TRY(rt_geom_scene_box(c->d_pbox, c->nprim, c->d_geom_box, s));
+  float box[6];
+  HIP_TRY(hipMemcpyAsync(box, c->d_geom_box + 6 * RT_GEOM_BOX_BLOCKS, sizeof box, hipMemcpyDeviceToHost, s));
+  // 3: the zero-normal risk flags of the objects the range touches, from all
+  // their triangles
+  {
+    const auto ob = [&](size_t p) {  // the object holding prim p (empty objects hold none)
+      return (uint32_t)(std::upper_bound(c->obj_start.begin(), c->obj_start.end(), (uint32_t)p) -
+                        c->obj_start.begin() - 1);
+    };
+    const uint32_t o0 = ob(first), o1 = ob(first + count - 1);
+    HIP_TRY(rt_geom_zero_risk(c->d_tri_prim, c->d_nrm, c->obj_start[o0], c->obj_start[o1 + 1], c->d_objflag, o0, o1,
+                              s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int a = 0; a < 3; a++) c->scene_lo[a] = box[a], c->scene_hi[a] = box[3 + a];
+  const auto t1 = clk::now();
+  // 4: the tree (FLAT: the prim-order records are the scene image)
+  if (c->dev_tree && (rc = tree_rebuild(c))) return rc;
+  scene_publish(c);
+  const auto t2 = clk::now();
+  // everything keyed on the geometry: dropped, and rebuilt where rt_hip_create
+  // or the context's settings had built it
+  c->d_prim_leaf.reset();
+  const bool had_mu = c->d_node_mu;
+  c->d_prim_mu.reset();
+  c->d_node_mu.reset();
+  c->d_sh_global.reset();
+  c->sh_ulps = -1.0f;
+  c->n_sh_global = 0;
+  c->sh_omax = 0.0f;
+  c->sh_mu_max = 1.0f;
+  c->info.shadow_global = 0;
+  c->info.shadow_mu_max = 0.0;
+  c->d_node_rf.reset();
+  c->rf_unbounded = 0;
+  lbuf_release(c);
+  if ((rc = scene_light_buffers(c))) return rc;
+  const auto t3 = clk::now();
+  if (had_mu && (rc = shadow_prepare(c, s))) return rc;
+  if (c->exact_refl && (rc = reflect_prepare(c, s))) return rc;
+  c->info.build_seconds = secs(t0, t2);
+  c->geom_seconds[0] = secs(t0, t1);
+  c->geom_seconds[1] = secs(t1, t2);
+  c->geom_seconds[2] = secs(t2, t3);
+  c->broken = 0;
+  c->geom_updates++;
+  return RT_OK;
+}
+
+// The refusals: nothing of the context has changed when one of them returns.
+static int geometry_refuse(const rt_hip_ctx* c, const void* triangles, size_t first, size_t count) {
+  if (!c) return rt_set_error(RT_EINVAL, "null context");
+  if (c->accel == RT_ACCEL_OCTREE && !c->dev_tree)
+    return rt_set_error(RT_EINVAL, "the context's octree was built on the host from the rt_scene (RT_ACCEL_OCTREE): "
+                                   "make a new context, or use RT_ACCEL_OCTREE_GPU");
+  if (first > c->nprim || count > c->nprim - first)
+    return rt_set_error(RT_EINVAL, "triangles [%zu, %zu + %zu) of %u", first, first, count, c->nprim);
+  if (count && !triangles) return rt_set_error(RT_EINVAL, "null triangles");
+  return RT_OK;
+}
+
+extern "C" int rt_hip_set_triangles(rt_hip_ctx* c, const void* d_triangles, size_t first, size_t count) {
+  const int rc = geometry_refuse(c, d_triangles, first, count);
+  if (rc || !count) return rc;
+  return geometry_update(c, (const float*)d_triangles, first, count);
+}
+
+static_assert(sizeof(rt_triangle) == 18 * sizeof(float), "rt_triangle is the 18 floats k_flatten reads");
+extern "C" int rt_hip_set_triangles_host(rt_hip_ctx* c, const rt_triangle* h_triangles, size_t first, size_t count) {
+  const int rc = geometry_refuse(c, h_triangles, first, count);
+  if (rc || !count) return rc;
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf<float> d_src;  // (nothing of the context is touched before the upload holds)
+  HIP_TRY(d_src.alloc(count * 18));
+  HIP_TRY(hipMemcpy(d_src, h_triangles, count * sizeof(rt_triangle), hipMemcpyHostToDevice));
+  return geometry_update(c, d_src, first, count);
+}
+
+extern "C" int rt_hip_geometry_updates(const rt_hip_ctx* c, unsigned long long* n) {
+  if (!c || !n) return rt_set_error(RT_EINVAL, "null argument");
+  *n = c->geom_updates;
+  return RT_OK;
+}
+
+extern "C" int rt_hip_geometry_times(const rt_hip_ctx* c, double seconds[3]) {
+  if (!c || !seconds) return rt_set_error(RT_EINVAL, "null argument");
+  for (int k = 0; k < 3; k++) seconds[k] = c->geom_seconds[k];
+  return RT_OK;
+}
+
 extern "C" int rt_hip_set_keep_visibility(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->keep_visibility = enable ? 1 : 0;  // (the mask buffer comes with the next render's hit buffers)
   return RT_OK;
 }
@@ -1139,6 +1331,7 @@ extern "C" int rt_hip_set_keep_visibility(rt_hip_ctx* c, int enable) {
 extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, float* d_tiles,
                               void* stream) {
   if (!c || !f || !d_tiles) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   // the refusals: nothing of the context has changed when one of them returns
   if (!c->rl_valid)
     return rt_set_error(RT_EINVAL, "no kept hit records: rt_hip_render first (rt_hip_render_compat keeps none)");
@@ -1218,6 +1411,7 @@ extern "C" int rt_hip_relight(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
 
 extern "C" int rt_hip_relight_image(rt_hip_ctx* c, const rt_frame* f, float* h_rgb, rt_stats* st) {
   if (!c || !f || !h_rgb) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   HIP_TRY(hipSetDevice(c->device));
   const size_t nt = rt_hip_tile_buffer_floats(f->width, f->height, 1);
@@ -1240,6 +1434,7 @@ static_assert(RT_GB_WORDS == RT_GB_WORDS_D && sizeof(rt_gsample) == 4 * RT_GB_WO
               "rt_gsample is the record gbuffer_kernel writes");
 extern "C" int rt_hip_set_gbuffer(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->gbuffer = enable ? 1 : 0;
   if (!c->gbuffer) c->gb_valid = 0;
   return RT_OK;
@@ -1252,6 +1447,7 @@ extern "C" size_t rt_hip_gbuffer_tile_words(int width, int height, int nranks) {
 extern "C" int rt_hip_gbuffer(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, void* d_tiles,
                               void* stream) {
   if (!c || !f || !d_tiles) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if ((uintptr_t)d_tiles & 7) return rt_set_error(RT_EINVAL, "G-buffer tiles must be 8-byte aligned");
   if (!c->gbuffer || !c->gb_valid)
     return rt_set_error(RT_EINVAL, "no G-buffer capture: rt_hip_set_gbuffer(1), then rt_hip_render");
@@ -1274,6 +1470,7 @@ extern "C" int rt_hip_gbuffer(rt_hip_ctx* c, const rt_frame* f, int rank, int nr
 extern "C" int rt_hip_assemble_gbuffer(rt_hip_ctx* c, const rt_frame* f, const void* d_gathered, int nranks,
                                        void* d_samples, void* stream) {
   if (!c || !f || !d_gathered || !d_samples || nranks <= 0) return rt_set_error(RT_EINVAL, "bad argument");
+  RT_CTX_LIVE(c);
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -1288,6 +1485,7 @@ extern "C" int rt_hip_assemble_gbuffer(rt_hip_ctx* c, const rt_frame* f, const v
 extern "C" int rt_hip_render_image_gbuffer(rt_hip_ctx* c, const rt_frame* f, float* h_rgb,
                                            rt_gsample* h_samples, rt_stats* st) {
   if (!c || !f || !h_rgb || !h_samples) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   HIP_TRY(hipSetDevice(c->device));
   const size_t nt = rt_hip_tile_buffer_floats(f->width, f->height, 1);
@@ -1330,6 +1528,7 @@ int choose_accel(const rt_scene* s);
 extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigned char* h_rgba,
                                     rt_stats* st) {
   if (!c || !cam || !h_rgba) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (cam->width <= 0 || cam->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   if ((long long)cam->width * cam->height > (1ll << 28) / 9)
     return rt_set_error(RT_EINVAL, "frame too large for the 3x render");

@@ -84,6 +84,7 @@ static int cand_verify(rt_hip_ctx* c, const rt_frame* f, KParams kp, int compat,
 extern "C" int rt_hip_cand_verify(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks,
                                   unsigned long long out[7]) {
   if (!c || !f || !out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (!c->d_cand_start || !c->d_cand || !c->d_cand_list)
     return rt_set_error(RT_EINVAL, "no candidate lists (render a frame with exact camera rays first)");
   if (c->last_p.rank != rank || c->last_p.nranks != nranks)
@@ -95,6 +96,7 @@ extern "C" int rt_hip_cand_verify(rt_hip_ctx* c, const rt_frame* f, int rank, in
 // camera's 3x frame, one sample per pixel (CandParams::compat), one rank.
 extern "C" int rt_hip_cand_verify_compat(rt_hip_ctx* c, const rt_camera* cam, unsigned long long out[7]) {
   if (!c || !cam || !out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (!c->d_cand_start || !c->d_cand || !c->d_cand_list)
     return rt_set_error(RT_EINVAL, "no candidate lists (render a frame with exact camera rays first)");
   rt_camera big = *cam;
@@ -161,6 +163,7 @@ static int cand_verify(rt_hip_ctx* c, const rt_frame* f, KParams kp, int compat,
 
 extern "C" int rt_hip_cand_tile_entries(rt_hip_ctx* c, unsigned int* out, size_t n) {
   if (!c || !out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (!c->d_cand_start) return rt_set_error(RT_EINVAL, "no candidate lists (render a frame first)");
   if (n > (size_t)c->last_p.ntiles_local)
     return rt_set_error(RT_EINVAL, "%zu tiles asked, the last render had %d", n, c->last_p.ntiles_local);
@@ -194,6 +197,7 @@ static constexpr uint32_t kItemCap = RT_CAND_ITEM_CAP;
 
 extern "C" int rt_hip_set_cand_item_cap(rt_hip_ctx* c, unsigned cap) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->cand_item_cap = cap;
   lists_changed(c);  // the lists change
   return RT_OK;
@@ -611,6 +615,7 @@ int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t cs, 
 extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, unsigned* counts,
                                    unsigned* nglobal_out, void* stream) {
   if (!c || !f || !counts || !nglobal_out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (nranks <= 0 || rank < 0 || rank >= nranks) return rt_set_error(RT_EINVAL, "rank %d of %d", rank, nranks);
   if (c->accel != RT_ACCEL_OCTREE || !c->d_node || !c->exact_camera)
     return rt_set_error(RT_EINVAL, "no camera candidate lists in this configuration (octree, exact camera rays)");
@@ -694,6 +699,7 @@ extern "C" int rt_hip_cand_produce(rt_hip_ctx* c, const rt_frame* f, int rank, i
 
 extern "C" int rt_hip_cand_send_buffer(const rt_hip_ctx* c, const void** d_entries, size_t* n) {
   if (!c || !d_entries || !n) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   *d_entries = c->d_send;
   *n = c->send_n;
   return RT_OK;
@@ -706,6 +712,7 @@ extern "C" int rt_hip_cand_send_buffer(const rt_hip_ctx* c, const void** d_entri
 extern "C" int rt_hip_cand_consume(rt_hip_ctx* c, const rt_frame* f, int rank, int nranks, const void* d_entries,
                                    size_t n, unsigned nglobal, void* stream) {
   if (!c || !f || (!d_entries && n)) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (nranks <= 0 || rank < 0 || rank >= nranks) return rt_set_error(RT_EINVAL, "rank %d of %d", rank, nranks);
   if (n >= (1ull << 31) || nglobal > n) return rt_set_error(RT_EINVAL, "%zu entries, %u globals", n, nglobal);
   HIP_TRY(hipSetDevice(c->device));

@@ -13,6 +13,7 @@
 static int occl_refuse(const rt_hip_ctx* c, const float* origins, const float* dirs, size_t n, unsigned flags,
                        const unsigned char* out) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   if (n > RT_RAYS_MAX)
     return rt_set_error(RT_EINVAL, "%zu rays: a batch holds at most %llu", n, (unsigned long long)RT_RAYS_MAX);
   if (n && (!origins || !dirs)) return rt_set_error(RT_EINVAL, "null rays");

@@ -12,6 +12,7 @@ static_assert(RT_RAYS_MAX == RT_RAY_BATCH_MAX, "rt_hip.h states what a record in
 static int rays_refuse(const rt_hip_ctx* c, const float* origins, const float* dirs, size_t n, unsigned flags,
                        const float* rgb, const void* samples) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   if (!rgb && !samples) return rt_set_error(RT_EINVAL, "a ray batch needs a colour or a sample output");
   if (n && (!origins || !dirs)) return rt_set_error(RT_EINVAL, "null rays");
   if (n > RT_RAYS_MAX)
@@ -133,6 +134,7 @@ extern "C" int rt_hip_trace_rays_host(rt_hip_ctx* c, const float* h_origins, con
 extern "C" int rt_hip_frame_rays(rt_hip_ctx* c, const rt_frame* f, int order, float* d_origins, float* d_dirs,
                                  void* stream) {
   if (!c || !f || !d_origins || !d_dirs) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   if ((f->width | f->height) & 1)
     return rt_set_error(RT_EINVAL, "frame %dx%d: cpu/rt renders even sizes only", f->width, f->height);
@@ -155,6 +157,7 @@ extern "C" int rt_hip_frame_rays(rt_hip_ctx* c, const rt_frame* f, int order, fl
 
 extern "C" int rt_hip_frame_rays_host(rt_hip_ctx* c, const rt_frame* f, int order, float* h_origins, float* h_dirs) {
   if (!c || !f || !h_origins || !h_dirs) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (f->width <= 0 || f->height <= 0) return rt_set_error(RT_EINVAL, "empty frame");
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = 12 * (size_t)f->width * (size_t)f->height;  // floats of 4 W H rays

@@ -95,6 +95,7 @@ extern "C" int rt_lightbuf_survey(const rt_scene* scene, unsigned light, int exa
 
 extern "C" int rt_hip_accel_validate(const rt_hip_ctx* c) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   HIP_TRY(hipSetDevice(c->device));
   rt_flat_scene f;
   std::memset(&f, 0, sizeof f);
@@ -119,6 +120,7 @@ extern "C" int rt_hip_accel_validate(const rt_hip_ctx* c) {
 
 extern "C" int rt_hip_set_timing(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   HIP_TRY(hipSetDevice(c->device));
   for (auto& f : c->ev)
     for (hipEvent_t& e : f)
@@ -130,6 +132,7 @@ extern "C" int rt_hip_set_timing(rt_hip_ctx* c, int enable) {
 
 extern "C" int rt_hip_frame_times(rt_hip_ctx* c, int n, float* lists_ms, float* render_ms) {
   if (!c || !lists_ms || !render_ms) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (n <= 0 || n > RT_TIMED_FRAMES || (unsigned long long)n > c->frames)
     return rt_set_error(RT_EINVAL, "%d timed frames asked, %llu recorded (ring of %d)", n,
                         c->frames, RT_TIMED_FRAMES);
@@ -148,6 +151,7 @@ extern "C" int rt_hip_frame_times(rt_hip_ctx* c, int n, float* lists_ms, float* 
 extern "C" int rt_hip_frame_kernel_times(rt_hip_ctx* c, int n, float* trace_ms, float* shade_ms,
                                          float* fold_ms) {
   if (!c || !trace_ms || !shade_ms || !fold_ms) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (n <= 0 || n > RT_TIMED_FRAMES || (unsigned long long)n > c->frames)
     return rt_set_error(RT_EINVAL, "%d timed frames asked, %llu recorded (ring of %d)", n,
                         c->frames, RT_TIMED_FRAMES);
@@ -164,6 +168,7 @@ extern "C" int rt_hip_frame_kernel_times(rt_hip_ctx* c, int n, float* trace_ms, 
 
 extern "C" int rt_hip_tile_cycles(rt_hip_ctx* c, unsigned long long* out, size_t n) {
   if (!c || !out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (!c->d_tile_cycles || n > c->tile_cycles_n)
     return rt_set_error(RT_EINVAL, "%zu tile clocks asked, %zu recorded (rt_hip_set_count_work)", n,
                         c->tile_cycles_n);
@@ -176,6 +181,7 @@ extern "C" int rt_hip_tile_cycles(rt_hip_ctx* c, unsigned long long* out, size_t
 
 extern "C" int rt_hip_tile_phase_cycles(rt_hip_ctx* c, int phase, unsigned long long* out, size_t n) {
   if (!c || !out || phase < 0 || phase > 5) return rt_set_error(RT_EINVAL, "bad argument");
+  RT_CTX_LIVE(c);
   if (!c->d_tile_cycles || n > c->tile_cycles_n)
     return rt_set_error(RT_EINVAL, "%zu item clocks asked, %zu recorded (rt_hip_set_count_work)", n,
                         c->tile_cycles_n);
@@ -189,6 +195,7 @@ extern "C" int rt_hip_tile_phase_cycles(rt_hip_ctx* c, int phase, unsigned long 
 
 extern "C" int rt_hip_set_count_work(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
   c->count_work = enable ? 1 : 0;
   return RT_OK;
 }
@@ -210,6 +217,7 @@ extern "C" int rt_hip_verify_shadows(rt_hip_ctx* c, unsigned stride, unsigned lo
 extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsigned first,
                                           unsigned long long out[4]) {
   if (!c || !out) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (!c->d_hit || !c->last_p.hit) return rt_set_error(RT_EINVAL, "no hit records (render a frame first)");
   if (c->nlight > 32) return rt_set_error(RT_EINVAL, "shadow verification covers at most 32 lights");
   HIP_TRY(hipSetDevice(c->device));
@@ -282,6 +290,7 @@ extern "C" int rt_hip_verify_shadows_from(rt_hip_ctx* c, unsigned stride, unsign
 extern "C" int rt_hip_probe_closest(rt_hip_ctx* c, const float* origins, const float* dirs, size_t n, int brute,
                                     unsigned* prim, float* dist) {
   if (!c || (n && (!origins || !dirs || !prim || !dist))) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (!brute && (c->accel != RT_ACCEL_OCTREE || !c->d_node || !c->d_spill))
     return rt_set_error(RT_EINVAL, "the walk probe needs an octree context");
   if (!c->d_tri_prim) return rt_set_error(RT_EINVAL, "no triangles");
@@ -325,6 +334,7 @@ extern "C" int rt_hip_probe_closest(rt_hip_ctx* c, const float* origins, const f
 extern "C" int rt_hip_probe_shadows(rt_hip_ctx* c, unsigned light, const float* origins, size_t n, int brute,
                                     unsigned char* hit) {
   if (!c || (!origins && n) || (!hit && n)) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   if (light >= c->nlight || (c->light_type[light] != 1 && c->light_type[light] != 2))
     return rt_set_error(RT_EINVAL, "light %u is not a directional or point light", light);
   if (n > (1u << 26)) return rt_set_error(RT_EINVAL, "%zu origins (at most 2^26 per call)", n);
@@ -361,6 +371,7 @@ extern "C" int rt_hip_probe_shadows(rt_hip_ctx* c, unsigned light, const float* 
 // own queries.
 extern "C" int rt_hip_frame_check(rt_hip_ctx* c, unsigned* flags, unsigned* frames, unsigned long long* queries) {
   if (!c || !flags || !frames || !queries) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
   *flags = *frames = 0;
   queries[0] = queries[1] = 0;
   if (!c->d_frame_check) return RT_OK;

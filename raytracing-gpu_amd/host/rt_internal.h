@@ -57,6 +57,7 @@ typedef struct rt_flat_scene {
   uint32_t root_count;      /* 1 (root is node 0) or 0 for FLAT              */
   float scene_lo[3], scene_hi[3];
   size_t leaves, max_depth, max_leaf;
+  float *pbox;              /* FLAT only: ntri * 6, each prim's vertex box lo.xyz hi.xyz */
 } rt_flat_scene;
 
 #define RT_TRI_FLOATS 12

@@ -205,6 +205,10 @@ _PROTOS = [
     ("rt_hip_set_lights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("rt_hip_set_materials", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("rt_hip_set_keep_visibility", C.c_int, [C.c_void_p, C.c_int]),
+    ("rt_hip_set_triangles", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    ("rt_hip_set_triangles_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]),
+    ("rt_hip_geometry_updates", C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    ("rt_hip_geometry_times", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("rt_hip_relight", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("rt_hip_relight_image", C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_void_p, C.POINTER(Stats)]),
     ("rt_hip_set_gbuffer", C.c_int, [C.c_void_p, C.c_int]),
@@ -329,6 +333,27 @@ class Scene:
         """All triangles as a (T, 6, 3) float32 array (vertices then normals)."""
         return scene_triangles(self.ptr)
 
+    def set_triangles_array(self, array, first=0):
+        """Write an (n, 6, 3) or (n, 18) float32 array (the layout of
+        triangles_array()) over the triangles [first, first + n) of the host
+        rt_scene, in prim order: the oracle and a fresh Context then see the
+        edited scene (Context.set_triangles edits a live context)."""
+        a = _triangle_rows(array)
+        first = int(first)
+        if first < 0 or first + len(a) > self.triangle_count:
+            raise IndexError(f"triangles [{first}, {first + len(a)}) of {self.triangle_count}")
+        s, base, done = self.s, 0, 0
+        for i in range(s.object_count):
+            o = s.objects[i]
+            n = int(o.triangle_count)
+            lo, hi = max(first, base), min(first + len(a), base + n)
+            if lo < hi:
+                dst = C.addressof(o.triangles.contents) + 72 * (lo - base)
+                C.memmove(dst, a[lo - first:hi - first].ctypes.data, 72 * (hi - lo))
+                done += hi - lo
+            base += n
+        assert done == len(a)
+
     def materials_array(self):
         return scene_materials(self.ptr)
 
@@ -387,6 +412,74 @@ def scene_triangles(ptr):
             buf = (C.c_float * (18 * n)).from_address(C.addressof(o.triangles.contents))
             out.append(np.frombuffer(buf, dtype=np.float32).reshape(n, 6, 3).copy())
     return np.concatenate(out) if out else np.zeros((0, 6, 3), np.float32)
+
+
+def _triangle_rows(array):
+    """(n, 18) contiguous float32 rows of an (n, 6, 3) or (n, 18) array."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    if a.ndim == 3 and a.shape[1:] == (6, 3):
+        a = a.reshape(len(a), 18)
+    if a.ndim != 2 or a.shape[1] != 18:
+        raise ValueError(f"triangles are (n, 6, 3) or (n, 18) float32, not {a.shape}")
+    return a
+
+
+# ---- moving geometry (include/rt_hip.h rt_hip_set_triangles) ----
+def object_range(scene, k):
+    """(first, count) of object k's triangles in prim order (object, then the
+    object's triangle index): the range rt_hip_set_triangles takes."""
+    s = _as_scene_ptr(scene.ptr if isinstance(scene, Scene) else scene).contents
+    if not 0 <= int(k) < s.object_count:
+        raise IndexError(f"object {k} of {s.object_count}")
+    first = sum(int(s.objects[i].triangle_count) for i in range(int(k)))
+    return first, int(s.objects[int(k)].triangle_count)
+
+
+def vertex_extent(tris):
+    """The float32 largest side of the vertex box of (n, 6, 3) triangles."""
+    v = np.asarray(tris, np.float32).reshape(-1, 6, 3)[:, :3].reshape(-1, 3)
+    return np.float32((v.max(axis=0) - v.min(axis=0)).max())
+
+
+def shift_triangles(tris, delta):
+    """Every vertex plus float32 `delta` (3 values), in float32; normals stay.
+    -> a new (n, 6, 3) float32 array."""
+    t = np.array(tris, np.float32).reshape(-1, 6, 3)
+    t[:, :3] = t[:, :3] + np.asarray(delta, np.float32)
+    return t
+
+
+def _rot_y(v, c, s):
+    """v @ R.T for R = [[c, 0, s], [0, 1, 0], [-s, 0, c]] in float32, each
+    component the products summed left to right (x R_i0 + y R_i1) + z R_i2."""
+    f32 = np.float32
+    x, y, z = v[..., 0], v[..., 1], v[..., 2]
+    return np.stack([(x * c + y * f32(0)) + z * s, (x * f32(0) + y * f32(1)) + z * f32(0),
+                     (x * -s + y * f32(0)) + z * c], axis=-1).astype(f32)
+
+
+def spin_triangles(tris, angle=0.3):
+    """The triangles turned by `angle` about the y axis through the float32
+    mean m of their vertices (the vertex rows summed in order, in float32,
+    divided by their count): vertices become (v - m) @ R.T + m, normals n @ R.T,
+    R = [[c, 0, s], [0, 1, 0], [-s, 0, c]], c, s = float32(cos angle),
+    float32(sin angle); float32 throughout.  -> a new (n, 6, 3) float32 array."""
+    f32 = np.float32
+    t = np.array(tris, f32).reshape(-1, 6, 3)
+    c, s = f32(np.cos(angle)), f32(np.sin(angle))
+    v = t[:, :3].reshape(-1, 3)
+    m = (np.cumsum(v, axis=0, dtype=f32)[-1] / f32(len(v))).astype(f32) if len(v) else np.zeros(3, f32)
+    t[:, :3] = _rot_y(t[:, :3] - m, c, s) + m
+    t[:, 3:] = _rot_y(t[:, 3:], c, s)
+    return t
+
+
+def scale_triangles(tris, factors=(1.0625, 0.9375, 1.125)):
+    """Every vertex times float32 `factors` (per axis), in float32; normals
+    stay.  -> a new (n, 6, 3) float32 array."""
+    t = np.array(tris, np.float32).reshape(-1, 6, 3)
+    t[:, :3] = t[:, :3] * np.asarray(factors, np.float32)
+    return t
 
 
 def scene_materials(ptr):
@@ -905,6 +998,35 @@ class Context:
         else:
             ptr, n = C.cast(scene_or_objects, C.c_void_p), len(scene_or_objects)
         _check(lib().rt_hip_set_materials(self.h, ptr, n), "rt_hip_set_materials")
+
+    def set_triangles(self, array, first=0):
+        """Replace the triangles [first, first + n) of the live context, in
+        prim order, by an (n, 6, 3) or (n, 18) float32 host array (the layout
+        of Scene.triangles_array(); rt_hip_set_triangles_host): everything that
+        depends on them is rebuilt on the device before this returns."""
+        a = _triangle_rows(array)
+        _check(lib().rt_hip_set_triangles_host(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None,
+                                               int(first), len(a)), "rt_hip_set_triangles_host")
+
+    def set_triangles_device(self, ptr, first, count):
+        """set_triangles from device memory of the context's device: `count`
+        records of 18 floats at `ptr` (a torch tensor's data_ptr();
+        rt_hip_set_triangles), read on the context's stream."""
+        _check(lib().rt_hip_set_triangles(self.h, C.c_void_p(ptr) if ptr else None, int(first), int(count)),
+               "rt_hip_set_triangles")
+
+    def geometry_updates(self):
+        """Successful geometry updates of this context so far."""
+        n = C.c_ulonglong()
+        _check(lib().rt_hip_geometry_updates(self.h, C.byref(n)), "rt_hip_geometry_updates")
+        return int(n.value)
+
+    def geometry_times(self):
+        """(flatten + box + flags, tree, light buffers) wall seconds of the
+        last successful geometry update (rt_hip_geometry_times)."""
+        t = (C.c_double * 3)()
+        _check(lib().rt_hip_geometry_times(self.h, t), "rt_hip_geometry_times")
+        return tuple(float(x) for x in t)
 
     def set_keep_visibility(self, on=True):
         """Renders keep each hit record's unshadowed-light mask, so the first
