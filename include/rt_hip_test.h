@@ -39,6 +39,24 @@ int rt_accel_probe(const rt_scene *scene, int accel, int sample_stride, int chec
 /* Downloads the context's scene image and checks the invariants of
  * rt_accel_validate on it (any accel, including device-built octrees). */
 int rt_hip_accel_validate(const rt_hip_ctx *ctx);
+/* The derived geometry word for word (tests/test_geometry_words.py).  All
+ * three are read-only: no kernel, no change to a context.
+ * Host-only: what rt_flatten derives from the scene's triangles in prim
+ * order -- the records (12 floats a prim: v0, e1, e2, prim, object, flags),
+ * the normalised normal rows (9), the vertex boxes (6: lo.xyz hi.xyz) and the
+ * scene box (lo.xyz hi.xyz).  rt_scene_triangle_count(scene) prims; a NULL
+ * output is skipped, all NULL is RT_EINVAL. */
+int rt_flatten_image(const rt_scene *scene, float *rec, float *nrm, float *pbox, float box[6]);
+/* The same four as the context holds them on the device (after the work on
+ * its stream): what rt_hip_create uploaded or rt_hip_set_triangles derived.
+ * pbox on a host-tree context (RT_ACCEL_OCTREE), which keeps none: RT_EINVAL. */
+int rt_hip_geometry_image(const rt_hip_ctx *ctx, float *rec, float *nrm, float *pbox, float box[6]);
+/* The scene image rt_hip_accel_validate checks: the walk's triangle records
+ * (leaf order under an octree, prim order on FLAT) and the nodes.  need[0] /
+ * [1] = their floats; both buffers NULL: only need is filled; a buffer
+ * smaller than its need: RT_EINVAL. */
+int rt_hip_scene_image(const rt_hip_ctx *ctx, float *tri, size_t tri_floats, float *node, size_t node_floats,
+                       size_t need[2]);
 /* Host-only self-check of the tile map's O(1) row arithmetic (the candidate
  * lists' counts and emission order) against a brute-force walk over the
  * frame's tiles: every tile row, column intervals [x0, x1] of every width

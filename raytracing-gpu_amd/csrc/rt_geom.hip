@@ -10,8 +10,9 @@
 //              (the 72-byte record stride never reaches memory).
 //   scene box  exact min / max over every prim's vertex box: per lane, across
 //              the wave, across the workgroup, then one workgroup over the
-//              partial boxes.  min and max are order-independent, so the result
-//              is rt_flatten's compare loop's for finite input.
+//              partial boxes.  rt_min_f / rt_max_f (host/rt_minmax.h, shared
+//              with rt_flatten) are order-independent down to the sign of a
+//              zero, so the result is rt_flatten's bit for bit for finite input.
 //   zero risk  the per-object flag of host/rt_zero_risk.h from the normal
 //              rows, stamped into float 11 of the objects' records.
 //
@@ -22,6 +23,7 @@
 
 #include "rt_device.h"
 #include "rt_kernels.h"
+#include "../host/rt_minmax.h"
 #include "../host/rt_zero_risk.h"
 
 namespace rtg {
@@ -56,9 +58,9 @@ __global__ __launch_bounds__(kBlock) void k_flatten(const float* __restrict__ sr
       n[3 * k] = nn.x, n[3 * k + 1] = nn.y, n[3 * k + 2] = nn.z;
     }
     float* b = &s_box[threadIdx.x * 6];
-    b[0] = fminf(v0.x, fminf(v1.x, v2.x)), b[3] = fmaxf(v0.x, fmaxf(v1.x, v2.x));
-    b[1] = fminf(v0.y, fminf(v1.y, v2.y)), b[4] = fmaxf(v0.y, fmaxf(v1.y, v2.y));
-    b[2] = fminf(v0.z, fminf(v1.z, v2.z)), b[5] = fmaxf(v0.z, fmaxf(v1.z, v2.z));
+    b[0] = rt_min_f(v0.x, rt_min_f(v1.x, v2.x)), b[3] = rt_max_f(v0.x, rt_max_f(v1.x, v2.x));
+    b[1] = rt_min_f(v0.y, rt_min_f(v1.y, v2.y)), b[4] = rt_max_f(v0.y, rt_max_f(v1.y, v2.y));
+    b[2] = rt_min_f(v0.z, rt_min_f(v1.z, v2.z)), b[5] = rt_max_f(v0.z, rt_max_f(v1.z, v2.z));
   }
   __syncthreads();
   const size_t p0 = (size_t)first + t0;
@@ -88,8 +90,8 @@ __device__ __forceinline__ Box box_reduce_block(Box b) {
   __shared__ float s_part[kBlock / 64][6];
   for (int a = 0; a < 3; a++)
     for (int d = 32; d > 0; d >>= 1) {
-      b.lo[a] = fminf(b.lo[a], __shfl_xor(b.lo[a], d));
-      b.hi[a] = fmaxf(b.hi[a], __shfl_xor(b.hi[a], d));
+      b.lo[a] = rt_min_f(b.lo[a], __shfl_xor(b.lo[a], d));
+      b.hi[a] = rt_max_f(b.hi[a], __shfl_xor(b.hi[a], d));
     }
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
@@ -98,8 +100,8 @@ __device__ __forceinline__ Box box_reduce_block(Box b) {
   if (threadIdx.x == 0)
     for (int w = 1; w < kBlock / 64; w++)
       for (int a = 0; a < 3; a++) {
-        b.lo[a] = fminf(b.lo[a], s_part[w][a]);
-        b.hi[a] = fmaxf(b.hi[a], s_part[w][3 + a]);
+        b.lo[a] = rt_min_f(b.lo[a], s_part[w][a]);
+        b.hi[a] = rt_max_f(b.hi[a], s_part[w][3 + a]);
       }
   return b;
 }
@@ -111,8 +113,8 @@ __global__ __launch_bounds__(kBlock) void k_box(const float* __restrict__ in, ui
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
     const float* q = in + 6 * i;
     for (int a = 0; a < 3; a++) {
-      b.lo[a] = fminf(b.lo[a], q[a]);
-      b.hi[a] = fmaxf(b.hi[a], q[3 + a]);
+      b.lo[a] = rt_min_f(b.lo[a], q[a]);
+      b.hi[a] = rt_max_f(b.hi[a], q[3 + a]);
     }
   }
   b = box_reduce_block(b);

@@ -118,6 +118,67 @@ extern "C" int rt_hip_accel_validate(const rt_hip_ctx* c) {
   return rt_flat_validate(&f);
 }
 
+// ---- the derived geometry, word for word (tests/test_geometry_words.py):
+// read-only views of what rt_flatten derives on the host and what a context
+// holds on the device.  None of them launches a kernel or changes a context.
+
+// rt_flatten(scene, RT_ACCEL_FLAT)'s prim-order records (12 floats a prim,
+// flag word included), normal rows (9), vertex boxes (6) and scene box (lo.xyz
+// hi.xyz; +-FLT_MAX for a scene without triangles).  A NULL output is skipped.
+extern "C" int rt_flatten_image(const rt_scene* scene, float* rec, float* nrm, float* pbox, float box[6]) {
+  if (!scene) return rt_set_error(RT_EINVAL, "null scene");
+  if (!rec && !nrm && !pbox && !box) return rt_set_error(RT_EINVAL, "no output asked for");
+  rt_flat_scene fs;
+  const int rc = rt_flatten(scene, RT_ACCEL_FLAT, &fs);
+  if (rc) return rc;
+  if (rec && fs.ntri) std::memcpy(rec, fs.tri, fs.ntri * RT_TRI_FLOATS * sizeof(float));
+  if (nrm && fs.ntri) std::memcpy(nrm, fs.nrm, fs.ntri * 9 * sizeof(float));
+  if (pbox && fs.ntri) std::memcpy(pbox, fs.pbox, fs.ntri * 6 * sizeof(float));
+  if (box)
+    for (int a = 0; a < 3; a++) box[a] = fs.scene_lo[a], box[3 + a] = fs.scene_hi[a];
+  rt_flat_free(&fs);
+  return RT_OK;
+}
+
+// The same four of a context, as they stand on the device after the work
+// queued on its stream: d_tri_prim, d_nrm, d_pbox, scene_lo / scene_hi.
+extern "C" int rt_hip_geometry_image(const rt_hip_ctx* c, float* rec, float* nrm, float* pbox, float box[6]) {
+  if (!c) return rt_set_error(RT_EINVAL, "null context");
+  RT_CTX_LIVE(c);
+  if (!rec && !nrm && !pbox && !box) return rt_set_error(RT_EINVAL, "no output asked for");
+  const size_t n = c->nprim;
+  if (pbox && n && !c->d_pbox.holds(n * 6))
+    return rt_set_error(RT_EINVAL, "the context keeps no vertex boxes (a host-built octree is never updated)");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (rec && n) HIP_TRY(hipMemcpy(rec, c->d_tri_prim, n * RT_TRI_FLOATS * sizeof(float), hipMemcpyDeviceToHost));
+  if (nrm && n) HIP_TRY(hipMemcpy(nrm, c->d_nrm, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+  if (pbox && n) HIP_TRY(hipMemcpy(pbox, c->d_pbox, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
+  if (box)
+    for (int a = 0; a < 3; a++) box[a] = c->scene_lo[a], box[3 + a] = c->scene_hi[a];
+  return RT_OK;
+}
+
+// What rt_hip_accel_validate downloads: d_tri (nrec records, leaf order under
+// an octree) and d_node.  need = {tri floats, node floats}; with both buffers
+// NULL only need is filled, a buffer too small is refused.
+extern "C" int rt_hip_scene_image(const rt_hip_ctx* c, float* tri, size_t tri_floats, float* node,
+                                  size_t node_floats, size_t need[2]) {
+  if (!c || !need) return rt_set_error(RT_EINVAL, "null argument");
+  RT_CTX_LIVE(c);
+  need[0] = (size_t)c->nrec * RT_TRI_FLOATS;
+  need[1] = c->d_node ? (size_t)c->info.nodes * RT_NODE_FLOATS : 0;
+  if (!tri && !node) return RT_OK;
+  if ((tri && tri_floats < need[0]) || (node && node_floats < need[1]))
+    return rt_set_error(RT_EINVAL, "scene image: %zu + %zu floats offered, %zu + %zu needed", tri ? tri_floats : 0,
+                        node ? node_floats : 0, need[0], need[1]);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (tri && need[0]) HIP_TRY(hipMemcpy(tri, c->d_tri, need[0] * sizeof(float), hipMemcpyDeviceToHost));
+  if (node && need[1]) HIP_TRY(hipMemcpy(node, c->d_node, need[1] * sizeof(float), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
 extern "C" int rt_hip_set_timing(rt_hip_ctx* c, int enable) {
   if (!c) return rt_set_error(RT_EINVAL, "null context");
   RT_CTX_LIVE(c);

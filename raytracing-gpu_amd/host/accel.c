@@ -37,6 +37,7 @@
 #include "rt_cull.h"
 #include "rt_internal.h"
 #include "rt_zero_risk.h"
+#include "rt_minmax.h"
 
 #define RT_OCT_LEAF 4
 #define RT_OCT_DEPTH 20
@@ -585,10 +586,11 @@ int rt_flatten(const rt_scene *s, int accel, rt_flat_scene *out)
       for (int a = 0; a < 3; a++)
       {
         float c0 = (&tr->vertex[0].x)[a], c1 = (&tr->vertex[1].x)[a], c2 = (&tr->vertex[2].x)[a];
-        pb[a] = fminf(c0, fminf(c1, c2));
-        pb[3 + a] = fmaxf(c0, fmaxf(c1, c2));
-        if (pb[a] < out->scene_lo[a]) out->scene_lo[a] = pb[a];
-        if (pb[3 + a] > out->scene_hi[a]) out->scene_hi[a] = pb[3 + a];
+        /* rt_minmax.h: the bits the device update's reduction gives, in any order */
+        pb[a] = rt_min_f(c0, rt_min_f(c1, c2));
+        pb[3 + a] = rt_max_f(c0, rt_max_f(c1, c2));
+        out->scene_lo[a] = rt_min_f(out->scene_lo[a], pb[a]);
+        out->scene_hi[a] = rt_max_f(out->scene_hi[a], pb[3 + a]);
       }
     }
   }

@@ -148,6 +148,10 @@ _PROTOS = [
     ("rt_hip_create", C.c_int, [C.c_int, C.POINTER(SceneStruct), C.c_int, C.POINTER(C.c_void_p)]),
     ("rt_hip_accel_info", C.c_int, [C.c_void_p, C.POINTER(AccelInfo)]),
     ("rt_hip_accel_validate", C.c_int, [C.c_void_p]),
+    ("rt_flatten_image", C.c_int, [C.POINTER(SceneStruct), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_geometry_image", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_scene_image", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
     ("rt_hip_destroy", None, [C.c_void_p]),
     ("rt_hip_tiles_per_rank", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("rt_hip_tile_buffer_floats", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
@@ -493,6 +497,21 @@ def scene_materials(ptr):
     return np.array(rows, np.float32).reshape(-1, 13)
 
 
+def _geometry_buffers(n):
+    """(records (n, 12), normal rows (n, 9), vertex boxes (n, 6), scene box (6,)) float32, to be filled."""
+    return [np.zeros(shape, np.float32) for shape in ((n, 12), (n, 9), (n, 6), (6,))]
+
+
+def flatten_arrays(scene):
+    """What the host flatten derives from the scene's triangles, in prim order
+    (rt_flatten_image, no device): the records (T, 12) -- v0, e1, e2, then the
+    prim, object and flag words as float32 bit patterns --, the normalised
+    normal rows (T, 9), the vertex boxes (T, 6) and the scene box (6,)."""
+    out = _geometry_buffers(scene.triangle_count)
+    _check(lib().rt_flatten_image(scene.ptr, *(a.ctypes.data_as(C.c_void_p) for a in out)), "rt_flatten_image")
+    return tuple(out)
+
+
 def accel_build_info(scene, accel="octree"):
     i = AccelInfo()
     a = ACCEL[accel] if isinstance(accel, str) else accel
@@ -759,6 +778,31 @@ class Context:
     def validate(self):
         """Invariants of the device scene image (rt_hip_accel_validate)."""
         _check(lib().rt_hip_accel_validate(self.h), "accel_validate")
+
+    def geometry_arrays(self, boxes=True):
+        """The context's own records, normal rows, vertex boxes and scene box
+        as they stand on the device, in flatten_arrays' layout
+        (rt_hip_geometry_image).  boxes=False: None for the vertex boxes (a
+        host-tree context keeps none)."""
+        out = _geometry_buffers(int(self.info()["triangles"]))
+        ptr = [a.ctypes.data_as(C.c_void_p) for a in out]
+        if not boxes:
+            ptr[2], out[2] = None, None
+        _check(lib().rt_hip_geometry_image(self.h, *ptr), "rt_hip_geometry_image")
+        return tuple(out)
+
+    def scene_image(self):
+        """(triangle records (nrec, 12), nodes (nodes, 8)) of the scene image
+        the kernels walk, as uint32 words (rt_hip_scene_image): leaf-order
+        records and the octree's nodes, or the prim-order records and no node
+        on a flat context."""
+        need = (C.c_size_t * 2)()
+        _check(lib().rt_hip_scene_image(self.h, None, 0, None, 0, need), "rt_hip_scene_image")
+        tri, node = np.zeros(int(need[0]), np.uint32), np.zeros(int(need[1]), np.uint32)
+        _check(lib().rt_hip_scene_image(self.h, tri.ctypes.data_as(C.c_void_p) if tri.size else None, tri.size,
+                                        node.ctypes.data_as(C.c_void_p) if node.size else None, node.size, need),
+               "rt_hip_scene_image")
+        return tri.reshape(-1, 12), node.reshape(-1, 8)
 
     def set_count_work(self, on=True):
         _check(lib().rt_hip_set_count_work(self.h, 1 if on else 0), "count_work")

@@ -4,6 +4,7 @@ tests/native/zero_risk_twin.cpp, built plain and with AddressSanitizer +
 UBSan), Scene.set_triangles_array against the oracle, object_range, and the
 edit helpers of rtgpu.py against a value table computed once by scalar float32
 arithmetic from their definitions.  No GPU: tests/test_geometry.py."""
+import ctypes as C
 import os
 import shutil
 import subprocess
@@ -150,3 +151,136 @@ def test_edit_helpers_reproduce_the_value_table(rt):
     assert np.array_equal(_bits(t), _bits(keep)), "the helpers return new arrays"
     # (n, 18) rows are accepted too
     assert np.array_equal(_bits(rt.scale_triangles(t.reshape(2, 18))), _bits(got["scale"]))
+
+
+# ---- the derived geometry, word for word (rt_flatten_image) ---------------------
+# The host flatten against the numpy float32 reference of
+# tests/geometry_words_util.py; the device side is tests/test_geometry_words.py.
+import glob
+import gzip
+
+import geometry_words_util as gw
+
+RT_EINVAL = -1
+GOLDEN_SCENES = sorted(os.path.basename(p)[:-len(".svati.gz")]
+                       for p in glob.glob(os.path.join(REPO, "tests", "golden", "scenes", "*.svati.gz")))
+ADVERSARIAL = ["twins", "room", "slivers"]
+
+
+def _flags_by_object(rec, counts):
+    """Word 11 is 0 or 1 and the same over each object.  (Which objects: the
+    predicate's truth table and rt_flatten's use of it are zero_risk_twin.cpp's.)"""
+    flag = gw.bits(rec)[:, 11]
+    assert set(np.unique(flag)) <= {0, 1}
+    at = 0
+    for c in counts:
+        assert len(set(flag[at:at + c].tolist())) <= 1, f"object of prims [{at}, {at + c})"
+        at += c
+    return flag
+
+
+def _check_host(rt, s, what):
+    arrays = rt.flatten_arrays(s)
+    counts = gw.object_counts(s)
+    flag = _flags_by_object(arrays[0], counts)
+    # (boxes by value: numpy's minimum / maximum leave the sign of a zero open)
+    gw.check_against_reference(arrays, s.triangles_array(), counts, flag, what, box_bits=False)
+    return arrays
+
+
+@pytest.mark.parametrize("name", GOLDEN_SCENES)
+def test_flatten_arrays_equal_the_numpy_reference(rt, scene_dir, name):
+    assert len(GOLDEN_SCENES) >= 18
+    s = rt.Scene.load_svati(os.path.join(scene_dir, name + ".svati"))
+    assert s.triangle_count > 0
+    _check_host(rt, s, name)
+
+
+@pytest.mark.parametrize("name", ADVERSARIAL)
+def test_flatten_arrays_equal_the_numpy_reference_adversarial(rt, tmp_path, name):
+    import adversarial_util as adv
+    case = next(c for c in adv.load_manifest() if c["scene"] == name and (c["width"], c["height"]) == (32, 18))
+    s = rt.Scene.load_svati(adv.scene_path(case, tmp_path))
+    _check_host(rt, s, name)
+
+
+def test_flatten_arrays_equal_the_numpy_reference_edge_scene(rt, tmp_path):
+    """The 1,900-prim scene of distinct words, then the tables of awkward
+    normals and vertices written over its first 257 triangles."""
+    tris = gw.distinct_triangles(1900, 20261020)
+    s = gw.checked_scene(rt, tmp_path / "edge.svati", tris, gw.EDGE_COUNTS)
+    rec, nrm, pbox, box = _check_host(rt, s, "edge scene")
+    assert not gw.bits(rec)[:, 11].any(), "the generated normals stay away from the risk"
+    # (no zero anywhere: these boxes are numpy's bit for bit)
+    gw.check_against_reference((rec, nrm, pbox, box), s.triangles_array(), gw.EDGE_COUNTS, np.zeros(1900), "edge scene")
+    t = s.triangles_array()
+    t[:257, 3:], idx = gw.normal_table(257)
+    s.set_triangles_array(t)
+    rec, nrm, _, _ = _check_host(rt, s, "normals table")
+    R = len(gw.NORMAL_ROWS)
+    assert np.isnan(nrm[gw.ROW_ZERO]).all() and np.isnan(nrm[gw.ROW_UNDERFLOW, [1, 2, 4, 5, 7, 8]]).all()
+    assert np.isinf(nrm[gw.ROW_UNDERFLOW, [0, 3, 6]]).all()
+    assert (nrm[gw.ROW_OVERFLOW] == 0).all() and (gw.bits(nrm[gw.ROW_OVERFLOW, :3]) >> 31).tolist() == [0, 1, 0]
+    assert idx[:R].tolist() == [[i] * 3 for i in range(R)]
+    assert (gw.bits(rec)[:300, 11] == 1).all() and not gw.bits(rec)[300:, 11].any(), "the all-zeros rows flag object 0"
+    t[:257, 3:] = gw.distinct_triangles(257, 7)[:, 3:]
+    t[:257, :3] = gw.vertex_table(257)
+    s.set_triangles_array(t)
+    _check_host(rt, s, "vertex table")
+
+
+def _single(rt, tmp_path, vertices):
+    """One-triangle-per-row scenes: the vertex rows written over a scene of
+    len(rows) clean triangles in one object."""
+    v = np.asarray(vertices, gw.F32).reshape(-1, 3, 3)
+    t = gw.distinct_triangles(len(v), 11)
+    s = gw.checked_scene(rt, tmp_path / "zeros.svati", t, (len(v),))
+    t = s.triangles_array()
+    t[:, :3] = v
+    s.set_triangles_array(t)
+    return s
+
+
+NEG0, POS0 = 0x80000000, 0x00000000
+
+
+def test_box_zeros_have_one_sign_whatever_the_vertex_order(rt, tmp_path):
+    """The sign of a zero in the vertex boxes and the scene box, pinned: of two
+    zeros the minimum is -0 and the maximum +0 (host/rt_minmax.h), in all six
+    vertex orders and both prim orders.  fminf / fmaxf, which the flatten used
+    before, chose by operand position (glibc: fminf(-0, +0) = +0, fminf(+0, -0)
+    = -0), so lo.x of (-0, +0, 5) was +0, of (+0, -0, 5) was -0, and the scene
+    box kept the first zero it met; the device's v_min3_f32 / v_max3_f32 gave
+    -0 / +0 throughout, so an updated context differed from a fresh one."""
+    lo_rows = [[(c, 1.0, 2.0) for c in order] for order in gw.ZERO_LO]   # x = the triple, y = 1, z = 2
+    hi_rows = [[(c, 1.0, 2.0) for c in order] for order in gw.ZERO_HI]
+    s = _single(rt, tmp_path, lo_rows + hi_rows)
+    _, _, pbox, box = rt.flatten_arrays(s)
+    pb = gw.bits(pbox)
+    assert (pb[:6, 0] == NEG0).all() and (pbox[:6, 3] == 5).all(), [hex(int(x)) for x in pb[:6, 0]]
+    assert (pb[6:, 3] == POS0).all() and (pbox[6:, 0] == -5).all(), [hex(int(x)) for x in pb[6:, 3]]
+    assert (gw.bits(box) == gw.bits(np.array([-5, 1, 2, 5, 1, 2], gw.F32))).all()
+    # the scene box: two triangles whose lo.x / hi.y are the two zeros, in both prim orders
+    a = [(NZ, NZ, 3.0), (NZ, NZ, 3.0), (NZ, NZ, 3.0)]
+    b = [(PZ, PZ, 3.0), (PZ, PZ, 3.0), (PZ, PZ, 3.0)]
+    for order in ([a, b], [b, a]):
+        s = _single(rt, tmp_path, order)
+        _, _, pbox, box = rt.flatten_arrays(s)
+        assert gw.bits(box).tolist() == [NEG0, NEG0, gw.bits(gw.F32(3))[()], POS0, POS0, gw.bits(gw.F32(3))[()]]
+        assert sorted(gw.bits(pbox)[:, 0].tolist()) == [POS0, NEG0]  # (each prim's own box keeps its own zero)
+
+
+NZ, PZ = gw.NZ, gw.PZ
+
+
+def test_word_hooks_refuse_null_arguments(rt, scene_dir):
+    L = rt.lib()
+    s = rt.Scene.load_svati(os.path.join(scene_dir, "cube.svati"))
+    box = np.zeros(6, np.float32)
+    assert L.rt_flatten_image(None, None, None, None, box.ctypes.data_as(C.c_void_p)) == RT_EINVAL
+    assert L.rt_flatten_image(s.ptr, None, None, None, None) == RT_EINVAL
+    assert L.rt_flatten_image(s.ptr, None, None, None, box.ctypes.data_as(C.c_void_p)) == 0  # a NULL output is skipped
+    assert np.array_equal(gw.bits(box), gw.bits(rt.flatten_arrays(s)[3])) and box[0] < box[3]
+    need = (C.c_size_t * 2)()
+    assert L.rt_hip_geometry_image(None, None, None, None, box.ctypes.data_as(C.c_void_p)) == RT_EINVAL
+    assert L.rt_hip_scene_image(None, None, 0, None, 0, need) == RT_EINVAL

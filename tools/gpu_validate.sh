@@ -9,7 +9,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; export TMPDIR=/tmp
 T=${1:?tag}; O=gpurun_out/${T}_val; mkdir -p $O
 # the suite is every tests/test_*.py marked gpu: the moving-geometry tests
-# (tests/test_geometry.py) run with it
+# (tests/test_geometry.py, and word for word tests/test_geometry_words.py) run with it
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest.log 2>&1 || { tail -60 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
 timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
