@@ -547,6 +547,72 @@ int rt_hip_occluded(rt_hip_ctx *ctx, const float *d_origins, const float *d_dirs
 int rt_hip_occluded_host(rt_hip_ctx *ctx, const float *h_origins, const float *h_dirs, const float *h_tmax,
                          size_t n, unsigned flags, unsigned char *h_occluded, rt_stats *stats);
 
+/* Ambient occlusion from G-buffer records (new): for each of n rt_gsample
+ * records in device memory -- a rank's tile buffer straight from
+ * rt_hip_gbuffer, the assembled samples, the records of a ray batch -- the
+ * number of its k hemisphere rays that are occluded within tmax.  The rays are
+ * made in the kernel; no ray array exists.  d_occluded[i] (one 32-bit word per
+ * record, 0..k) is written exactly once for every i < n, nothing past n; the
+ * output needs no clearing.
+ *
+ * The ray rule (csrc/rt_ao_items.h is its one statement, rtgpu.ao_rays_host
+ * its numpy float32 twin; every step is a correctly rounded float operation in
+ * the written order, no FMA, so host and device agree in every bit):
+ *   shoots   s = (N.x N.x + N.y N.y) + N.z N.z in float, l = (float)sqrt((double)s);
+ *            record i shoots iff prim >= 0 and 0 < l < +inf.  A miss and a NaN,
+ *            zero, underflowing or overflowing normal do not: count 0.
+ *   frame    n = N / l;  sg = copysignf(1, n.z);  a = -1 / (sg + n.z);
+ *            b = n.x n.y a;  T = (1 + sg n.x n.x a, sg b, -sg n.x);
+ *            B = (b, sg + n.y n.y a, -n.y), each product left to right.  No
+ *            sine or cosine anywhere.
+ *   hash     g = base + i (64-bit);  h = mix32((uint32)g ^ mix32((uint32)(g >> 32) + seed)),
+ *            mix32(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16.
+ *   ray r    (0 <= r < k) takes row ((h >> 3) % m + r) % m of d_table (m rows of
+ *            3 floats, local directions with z > 0 about +z, e.g. cosine
+ *            weighted unit vectors); bit 0 of h swaps the row's x and y, then
+ *            bit 1 negates x and bit 2 negates y;  d = (x T + y B) + z n per
+ *            component, not normalised afterwards; the origin is P.
+ * `base` is the index of record 0 in the caller's whole set: a set cut into
+ * pieces, each with its base, gives the whole set's words.
+ *
+ * Each generated ray is then exactly ray j of an occlusion batch with
+ * d_tmax[j] = tmax (rt_hip_occluded above): the same traced / query rules (a
+ * non-finite P, a NaN tmax: not traced; tmax <= 0: no query), the same walks,
+ * RT_RAYS_PACKET with the same meaning (each work item's rays as one packet:
+ * the same counts), the same answer on FLAT, octree and proven contexts.
+ * tmax = +inf is has_direct_hit.  A record's count is the number of its k rays
+ * whose byte would be 1.  rt_hip_ao_rays writes the rays themselves, in ray
+ * order j = i k + r, 3 floats each for origin and direction -- zeros for a
+ * record that does not shoot, a ray no batch traces -- and, if d_shot is not
+ * NULL, one byte per record saying whether it shot.
+ *
+ * To the context the call is an occlusion batch: the kept frame survives it,
+ * rt_hip_stats directly after reads camera = rays traced, shadow = queries,
+ * depth_overflow, shadow_zero_risk and closest_unproven as counted and every
+ * other counter 0; a streaming caller's frames are unchanged.  Asynchronous on
+ * `stream`.  RT_EINVAL with nothing changed: a NULL context; NULL samples,
+ * table or output with n > 0; samples not 8-byte aligned; k == 0 or k >
+ * RT_AO_KMAX; m == 0; n k > RT_RAYS_MAX; flags other than RT_RAYS_PACKET; a
+ * non-default traversal policy; rt_hip_set_count_work.  n == 0 returns RT_OK
+ * and writes nothing. */
+#define RT_AO_KMAX 1024
+int rt_hip_ambient_occlusion(rt_hip_ctx *ctx, const void *d_samples, size_t n, unsigned long long base,
+                             unsigned k, const float *d_table, unsigned m, unsigned seed, float tmax,
+                             unsigned flags, unsigned *d_occluded, void *stream);
+/* Upload, rt_hip_ambient_occlusion on the context's stream, download,
+ * rt_hip_stats; synchronous. */
+int rt_hip_ambient_occlusion_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n,
+                                  unsigned long long base, unsigned k, const float *h_table, unsigned m,
+                                  unsigned seed, float tmax, unsigned flags, unsigned *h_occluded,
+                                  rt_stats *stats);
+int rt_hip_ao_rays(rt_hip_ctx *ctx, const void *d_samples, size_t n, unsigned long long base, unsigned k,
+                   const float *d_table, unsigned m, unsigned seed, float *d_origins, float *d_dirs,
+                   unsigned char *d_shot /* may be NULL */, void *stream);
+/* Upload, rt_hip_ao_rays on the context's stream, download; synchronous. */
+int rt_hip_ao_rays_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n, unsigned long long base,
+                        unsigned k, const float *h_table, unsigned m, unsigned seed, float *h_origins,
+                        float *h_dirs, unsigned char *h_shot /* may be NULL */);
+
 /* gpu/rt compatibility mode (gpu/raytracer.cu:31-129,
  * gpu/light.cu, gpu/colors.cu): the camera's frame rendered at 3x width and
  * height with one ray per high-resolution pixel, uint8 saturating colours,

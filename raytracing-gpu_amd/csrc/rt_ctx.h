@@ -11,6 +11,7 @@
 //   rt_multi.cpp   rt_raytrace_multi: N GPUs, RCCL exchange and gather
 //   rt_rays.cpp    rt_hip_trace_rays, rt_hip_frame_rays: a caller's ray batches
 //   rt_occl.cpp    rt_hip_occluded: a caller's occlusion batches
+//   rt_ao.cpp      rt_hip_ambient_occlusion: occlusion counts per G-buffer record
 // Internal, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -179,6 +180,7 @@ struct rt_hip_ctx {
   // block then; every render, relight, ray batch and compat render clears it
   DevBuf<unsigned long long> d_occl_stats;
   int occl_grid = 0;                // the kernel's persistent grid (0: not asked yet)
+  int ao_grid[2] = {0, 0};          // ao_kernel's, k <= 64 and k > 64 (csrc/rt_ao.cpp)
   int last_occl = 0;
   hipStream_t occl_stream = nullptr;
   KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here

@@ -242,6 +242,26 @@ struct OcclArgs {
   unsigned char* out;    // one byte per ray
 };
 
+// What the ambient-occlusion kernels take beside the KParams (csrc/rt_ao.h):
+// records in, the ray rule's inputs (csrc/rt_ao_items.h), one count per record
+// out.  ao_rays_kernel reads the first block only and writes org, dir, shot.
+struct AoArgs {
+  const uint2* samples;     // n rt_gsample records as five 8-byte pairs each
+  unsigned long long n;     // samples
+  unsigned long long base;  // index offset of sample 0 (the hash's 64-bit g = base + i)
+  const float* table;       // m local directions, 3 floats each
+  uint32_t k, m, seed;      // rays per sample, table rows, hash seed
+  uint32_t spi;             // rt_ao_spi(k): samples of a work item
+  uint32_t kinv;            // rt_ao_kinv(k): a lane's sample without a division
+  uint32_t nitems;          // rt_ao_item_count(n, k)
+  uint32_t walk;            // RT_RAYS_WALK_*, as OcclArgs::walk
+  float tmax;               // the batch's one distance bound (+inf: none)
+  uint32_t* out;            // one count per sample
+  float* org;               // ao_rays_kernel: 3 floats per ray
+  float* dir;               // ao_rays_kernel: 3 floats per ray
+  unsigned char* shot;      // ao_rays_kernel: one byte per sample, or NULL
+};
+
 // The three launches of one render (policy = RT_POLICY_*, octree only):
 // trace (closest hits -> hit records), shade (shadow queries + Phong per
 // record -> terms), fold (terms -> the rank's tile buffer)
@@ -293,6 +313,12 @@ extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* o
 // pulling items of 64 rays, and that kernel's persistent grid on `cus` CUs
 extern "C" hipError_t rt_launch_occl(const KParams* p, const OcclArgs* a, int accel, int grid, hipStream_t stream);
 extern "C" hipError_t rt_occl_grid(int accel, int cus, int* grid);
+// Ambient occlusion from records (csrc/rt_ao.h): the fused kernel (generate,
+// walk, count) on one-wave workgroups pulling items of whole samples, its
+// persistent grid (k <= 64 and k > 64 are two kernels), and the generator alone, one thread per ray
+extern "C" hipError_t rt_launch_ao(const KParams* p, const AoArgs* a, int accel, int grid, hipStream_t stream);
+extern "C" hipError_t rt_ao_grid(int accel, int wide, int cus, int* grid);  // wide: k > 64
+extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

@@ -771,7 +771,8 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
 #include "rt_recolour.h"  // relight_zero_kernel, recolour_kernel: after every render kernel
 #include "rt_shade_tables.h"  // shade_tables_kernel: after those
 #include "rt_rays.h"  // the ray batches' kernels: after those
-#include "rt_occl.h"  // the occlusion batches' kernel: last
+#include "rt_occl.h"  // the occlusion batches' kernel: after those
+#include "rt_ao.h"  // ambient occlusion from records: last
 
 // ---------------------------------------------------------------- launchers
 // One instantiation per (kernel, accel, work counting, policy); the default
@@ -1031,4 +1032,35 @@ extern "C" hipError_t rt_launch_occl(const KParams* p, const OcclArgs* a, int ac
   if (grid <= 0) return hipErrorInvalidValue;
   void* args[] = {(void*)p, (void*)a};
   return hipLaunchKernel(occl_kernel_of(accel), dim3(grid), dim3(64), args, 0, stream);
+}
+
+// Ambient occlusion from records (rt_kernels.h, csrc/rt_ao.h).  Last, for the
+// same reason once more: every earlier kernel keeps its place.
+static const void* ao_kernel_of(int accel, bool wide) {  // wide: k > 64
+  if (accel == RT_ACCEL_FLAT_D)
+    return wide ? (const void*)rt::ao_kernel<RT_ACCEL_FLAT_D, true> : (const void*)rt::ao_kernel<RT_ACCEL_FLAT_D, false>;
+  return wide ? (const void*)rt::ao_kernel<RT_ACCEL_OCTREE_D, true> : (const void*)rt::ao_kernel<RT_ACCEL_OCTREE_D, false>;
+}
+
+extern "C" hipError_t rt_ao_grid(int accel, int wide, int cus, int* grid) {
+  int per_cu = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ao_kernel_of(accel, wide != 0), 64, 0);
+  if (e != hipSuccess) return e;
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 32) per_cu = 32;
+  *grid = per_cu * cus;
+  return hipSuccess;
+}
+
+extern "C" hipError_t rt_launch_ao(const KParams* p, const AoArgs* a, int accel, int grid, hipStream_t stream) {
+  if (grid <= 0) return hipErrorInvalidValue;
+  void* args[] = {(void*)p, (void*)a};
+  return hipLaunchKernel(ao_kernel_of(accel, a->k > 64u), dim3(grid), dim3(64), args, 0, stream);
+}
+
+extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream) {
+  const unsigned long long blocks = (a->n * a->k + 255) / 256;
+  if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((rt::ao_rays_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
+  return hipGetLastError();
 }

@@ -232,6 +232,15 @@ _PROTOS = [
                                   C.c_void_p]),
     ("rt_hip_occluded_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint,
                                        C.c_void_p, C.POINTER(Stats)]),
+    ("rt_hip_ambient_occlusion", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p,
+                                           C.c_uint, C.c_uint, C.c_float, C.c_uint, C.c_void_p, C.c_void_p]),
+    ("rt_hip_ambient_occlusion_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint,
+                                                C.c_void_p, C.c_uint, C.c_uint, C.c_float, C.c_uint, C.c_void_p,
+                                                C.POINTER(Stats)]),
+    ("rt_hip_ao_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p, C.c_uint,
+                                 C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_ao_rays_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p,
+                                      C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_malloc", C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("rt_hip_free", C.c_int, [C.c_void_p]),
     ("rt_hip_memcpy_d2h", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -751,6 +760,83 @@ def hemisphere_rays(P, N, k, seed):
     return o.astype(np.float32), d.reshape(-1, 3).astype(np.float32)
 
 
+AO_KMAX = 1024  # RT_AO_KMAX
+
+
+def ao_table(m, seed):
+    """m local directions for Context.ambient_occlusion: cosine-weighted about
+    +z, unit length, z > 0 (the radius is kept off 1, as hemisphere_rays does)
+    -> (m, 3) float32, seeded."""
+    rng = np.random.default_rng(seed)
+    r = np.sqrt(rng.random(m)) * 0.999
+    phi = 2.0 * np.pi * rng.random(m)
+    t = np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r * r)], axis=1)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    return t.astype(np.float32)
+
+
+def _ao_mix32(x):
+    x = x.astype(np.uint32)
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7feb352d)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846ca68b)
+    return x ^ (x >> np.uint32(16))
+
+
+def ao_hash(n, seed, base=0):
+    """The hash of samples base .. base + n - 1 (csrc/rt_ao_items.h rt_ao_hash) -> uint32 (n,)."""
+    g = np.uint64(base) + np.arange(n, dtype=np.uint64)
+    lo, hi = (g & np.uint64(0xffffffff)).astype(np.uint32), (g >> np.uint64(32)).astype(np.uint32)
+    return _ao_mix32(lo ^ _ao_mix32(hi + np.uint32(seed & 0xffffffff)))
+
+
+def ao_rays_host(samples, k, table, seed, base=0):
+    """The numpy float32 twin of csrc/rt_ao_items.h: the k rays of every
+    GSAMPLE record, bit for bit what the device generates (every step one
+    correctly rounded float32 operation in the header's order) -> (origins,
+    dirs) (n k, 3) float32 in ray order i k + r, zeros for a record that does
+    not shoot, and the shot mask, bool (n,)."""
+    smp = np.ascontiguousarray(samples, dtype=GSAMPLE).reshape(-1)
+    tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 3)
+    n, m = len(smp), len(tab)
+    assert 1 <= k <= AO_KMAX and m >= 1
+    f = np.float32
+    N, P = smp["N"].astype(f), smp["P"].astype(f)
+    with np.errstate(all="ignore"):
+        s = (N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1]) + N[:, 2] * N[:, 2]
+        l = np.sqrt(s.astype(np.float64)).astype(f)
+        shot = (smp["prim"] >= 0) & (l > 0) & (l < np.inf)
+        nx, ny, nz = N[:, 0] / l, N[:, 1] / l, N[:, 2] / l
+        sg = np.copysign(f(1), nz)
+        a = f(-1) / (sg + nz)
+        b = nx * ny * a
+        T = np.stack([f(1) + sg * nx * nx * a, sg * b, -sg * nx], axis=1)
+        B = np.stack([b, sg + ny * ny * a, -ny], axis=1)
+        nn = np.stack([nx, ny, nz], axis=1)
+        h = ao_hash(n, seed, base)
+        rows = ((h >> np.uint32(3)) % np.uint32(m))[:, None].astype(np.uint64) + np.arange(k, dtype=np.uint64)[None, :]
+        row = tab[(rows % np.uint64(m)).astype(np.int64)]  # (n, k, 3)
+        swap = ((h & np.uint32(1)) != 0)[:, None]
+        x = np.where(swap, row[..., 1], row[..., 0])
+        y = np.where(swap, row[..., 0], row[..., 1])
+        x = np.where(((h & np.uint32(2)) != 0)[:, None], -x, x)
+        y = np.where(((h & np.uint32(4)) != 0)[:, None], -y, y)
+        z = row[..., 2]
+        d = (x[..., None] * T[:, None, :] + y[..., None] * B[:, None, :]) + z[..., None] * nn[:, None, :]
+    d = np.where(shot[:, None, None], d, f(0)).astype(f)
+    o = np.where(shot[:, None, None], np.broadcast_to(P[:, None, :], d.shape), f(0)).astype(f)
+    return o.reshape(-1, 3), d.reshape(-1, 3), shot
+
+
+def ao_open_share(counts, samples, k):
+    """The unoccluded share per sample from Context.ambient_occlusion's
+    counts: 1 - count / k; a sample that did not shoot counts as open."""
+    c = np.asarray(counts, dtype=np.float64).reshape(-1)
+    assert len(c) == len(np.asarray(samples).reshape(-1)) and k >= 1
+    return 1.0 - c / float(k)
+
+
 class Context:
     """One device image of a scene (rt_hip_create); renders through the C ABI."""
 
@@ -1196,6 +1282,55 @@ class Context:
             t.ctypes.data_as(C.c_void_p) if t is not None else None, len(o), RT_RAYS_PACKET if packet else 0,
             out.ctypes.data_as(C.c_void_p), C.byref(st))), "rt_hip_occluded_host")
         return out, st.as_dict()
+
+    def ambient_occlusion_device(self, d_samples, n, k, d_table, m, seed, d_out, tmax=None, packet=False, base=0,
+                                 stream=None):
+        """rt_hip_ambient_occlusion on device pointers (asynchronous): d_samples
+        = n GSAMPLE records (a tile buffer, assembled samples, a ray batch's
+        records), d_table = m rows of 3 floats, d_out receives n uint32 counts."""
+        _check(lib().rt_hip_ambient_occlusion(
+            self.h, C.c_void_p(d_samples) if d_samples else None, int(n), int(base), int(k),
+            C.c_void_p(d_table) if d_table else None, int(m), int(seed) & 0xffffffff,
+            float(np.inf if tmax is None else tmax), RT_RAYS_PACKET if packet else 0,
+            C.c_void_p(d_out) if d_out else None, C.c_void_p(stream) if stream else None), "rt_hip_ambient_occlusion")
+
+    def ambient_occlusion(self, samples, k, table, seed, tmax=None, packet=False, base=0):
+        """How many of each GSAMPLE record's k hemisphere rays are occluded
+        within tmax (None: no bound)?  The rays are ao_rays_host's, made on the
+        device (rt_hip_ambient_occlusion_host) -> (uint32 (n,), stats: those
+        of the occlusion batch of the same rays)."""
+        smp = np.ascontiguousarray(samples, dtype=GSAMPLE).reshape(-1)
+        tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(smp), np.uint32)
+        st = Stats()
+        self.last_rc = 0  # the call's return code (RT_EINEXACT passes _check_render after a parity-breaking knob)
+        self._check_render(self._keep_rc(lib().rt_hip_ambient_occlusion_host(
+            self.h, smp.ctypes.data_as(C.c_void_p), len(smp), int(base), int(k), tab.ctypes.data_as(C.c_void_p),
+            len(tab), int(seed) & 0xffffffff, float(np.inf if tmax is None else tmax),
+            RT_RAYS_PACKET if packet else 0, out.ctypes.data_as(C.c_void_p), C.byref(st))),
+            "rt_hip_ambient_occlusion_host")
+        return out, st.as_dict()
+
+    def ao_rays_device(self, d_samples, n, k, d_table, m, seed, d_origins, d_dirs, d_shot=0, base=0, stream=None):
+        """rt_hip_ao_rays on device pointers (asynchronous)."""
+        _check(lib().rt_hip_ao_rays(self.h, C.c_void_p(d_samples) if d_samples else None, int(n), int(base), int(k),
+                                    C.c_void_p(d_table) if d_table else None, int(m), int(seed) & 0xffffffff,
+                                    C.c_void_p(d_origins) if d_origins else None,
+                                    C.c_void_p(d_dirs) if d_dirs else None, C.c_void_p(d_shot) if d_shot else None,
+                                    C.c_void_p(stream) if stream else None), "rt_hip_ao_rays")
+
+    def ao_rays(self, samples, k, table, seed, base=0):
+        """The rays the device generates for GSAMPLE records (rt_hip_ao_rays)
+        -> (origins, dirs) (n k, 3) float32 and the shot mask: ao_rays_host's."""
+        smp = np.ascontiguousarray(samples, dtype=GSAMPLE).reshape(-1)
+        tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 3)
+        n, nr = len(smp), len(smp) * int(k)
+        o, d, shot = np.zeros((nr, 3), np.float32), np.zeros((nr, 3), np.float32), np.zeros(n, np.uint8)
+        _check(lib().rt_hip_ao_rays_host(self.h, smp.ctypes.data_as(C.c_void_p), n, int(base), int(k),
+                                         tab.ctypes.data_as(C.c_void_p), len(tab), int(seed) & 0xffffffff,
+                                         o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p),
+                                         shot.ctypes.data_as(C.c_void_p)), "rt_hip_ao_rays_host")
+        return o, d, shot.astype(bool)
 
     def render_compat(self, camera):
         """gpu/rt compatibility mode (rt_hip_render_compat) -> (H, W, 4)
