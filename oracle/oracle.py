@@ -52,6 +52,11 @@ def lib():
         L.oracle_camera_tri_accepts.restype = None
         L.oracle_camera_tri_accepts_gpu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.oracle_camera_tri_accepts_gpu.restype = None
+        L.oracle_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.POINTER(Counts)]
+        L.oracle_trace_rays.restype = C.c_int
+        L.oracle_spec_pow_ld_to.argtypes = [C.c_double, C.c_double, C.c_void_p]
+        L.oracle_spec_pow_ld_to.restype = None
         L.oracle_init_color.argtypes = [C.c_float, C.c_float, C.c_float]
         L.oracle_init_color.restype = ColorS
         L.oracle_color_add.argtypes = [ColorS, ColorS]
@@ -153,6 +158,41 @@ def render(scene_ptr, width, height, pixels=None, threads=0):
     if pixels is None:
         out = out.reshape(height, width, 3)
     return out, counts
+
+
+# struct or_first_hit (oracle/rt_oracle.h)
+FIRST_HIT = np.dtype([("obj", np.int32), ("P", np.float32, 3), ("N", np.float32, 3)])
+
+
+def trace_rays(scene_ptr, origins, dirs, threads=0, first=False):
+    """trace(ray, 1.0) of cpu/raytracer.c:19-34 per caller-supplied ray
+    (oracle_trace_rays; directions used as given).  origins, dirs: (n, 3)
+    float32.  Returns (rgb (n, 3) float32, FIRST_HIT records (n,) of the first
+    hits -- obj -1: none -- or None, counts dict)."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    assert len(o) == len(d)
+    rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))  # struct or_ray: origin, direction
+    out = np.zeros((len(o), 3), np.float32)
+    hits = np.zeros(len(o), FIRST_HIT) if first else None
+    cnt = Counts()
+    ptr = scene_ptr.ptr if isinstance(scene_ptr, OracleScene) else scene_ptr
+    if not isinstance(ptr, C.c_void_p):
+        ptr = C.cast(ptr, C.c_void_p)
+    rc = lib().oracle_trace_rays(ptr, rays.ctypes.data_as(C.c_void_p), len(o), threads,
+                                 out.ctypes.data_as(C.c_void_p),
+                                 hits.ctypes.data_as(C.c_void_p) if first else None, C.byref(cnt))
+    if rc != 0:
+        raise RuntimeError(f"oracle_trace_rays = {rc}")
+    return out, hits, {"closest": cnt.closest, "shadow": cnt.shadow, "max_depth": cnt.max_depth}
+
+
+def spec_pow_ld(x, e):
+    """powl(fmaxl(x, 0), e) as a numpy longdouble (oracle_spec_pow_ld; through
+    memory, since ctypes would hand the result over as a double)."""
+    out = np.zeros(1, np.longdouble)
+    lib().oracle_spec_pow_ld_to(float(x), float(e), out.ctypes.data_as(C.c_void_p))
+    return out[0]
 
 
 def camera_tri_accepts(scene_ptr, tris, rects, gpu=False):

@@ -735,6 +735,104 @@ static int run_job(struct job *jb, int nthreads, struct or_counts *counts)
   return 0;
 }
 
+/* ---- caller-supplied rays: trace(ray, 1.0) of cpu/raytracer.c:19-34 per ray ---- */
+
+struct ray_job {
+  const struct or_scene *scene;
+  const ray *rays;
+  size_t n;
+  float *out;
+  struct or_first_hit *first;
+  atomic_size_t next;
+  pthread_mutex_t lock;
+  struct or_counts total;
+};
+
+static void *ray_worker(void *arg)
+{
+  struct ray_job *jb = arg;
+  struct tls_counts cnt = { 0, 0, 0 };
+  for (;;)
+  {
+    size_t start = atomic_fetch_add(&jb->next, 16);
+    if (start >= jb->n)
+      break;
+    size_t stop = start + 16 < jb->n ? start + 16 : jb->n;
+    for (size_t p = start; p < stop; p++)
+    {
+      color c = trace(jb->scene, jb->rays[p], 1, 0, &cnt);
+      jb->out[3 * p + 0] = c.r;
+      jb->out[3 * p + 1] = c.g;
+      jb->out[3 * p + 2] = c.b;
+      if (jb->first)
+      {
+        /* the first query again, outside the counters */
+        struct or_first_hit *f = &jb->first[p];
+        int oi = -1;
+        ray hit = oracle_collide(jb->scene, jb->rays[p], &oi);
+        memset(f, 0, sizeof *f);
+        f->obj = -1;
+        if (!v_is_zero(hit.direction))
+        {
+          f->obj = oi;
+          f->P = hit.origin;
+          f->N = hit.direction;
+        }
+      }
+    }
+  }
+  pthread_mutex_lock(&jb->lock);
+  jb->total.closest += cnt.closest;
+  jb->total.shadow += cnt.shadow;
+  if (cnt.max_depth > jb->total.max_depth)
+    jb->total.max_depth = cnt.max_depth;
+  pthread_mutex_unlock(&jb->lock);
+  return NULL;
+}
+
+int oracle_trace_rays(const struct or_scene *scene, const struct or_ray *rays, size_t n, int nthreads,
+                      float *out_rgb, struct or_first_hit *out_first, struct or_counts *counts)
+{
+  if (!scene || !out_rgb || (n && !rays))
+    return -1;
+  struct ray_job jb;
+  memset(&jb, 0, sizeof jb);
+  jb.scene = scene;
+  jb.rays = rays;
+  jb.n = n;
+  jb.out = out_rgb;
+  jb.first = out_first;
+  if (nthreads <= 0)
+    nthreads = (int)sysconf(_SC_NPROCESSORS_ONLN);
+  if (nthreads < 1)
+    nthreads = 1;
+  atomic_init(&jb.next, 0);
+  pthread_mutex_init(&jb.lock, NULL);
+  pthread_t *tid = calloc((size_t)nthreads, sizeof *tid);
+  if (!tid)
+    return -1;
+  for (int t = 0; t < nthreads; t++)
+    pthread_create(&tid[t], NULL, ray_worker, &jb);
+  for (int t = 0; t < nthreads; t++)
+    pthread_join(tid[t], NULL);
+  free(tid);
+  pthread_mutex_destroy(&jb.lock);
+  if (counts)
+    *counts = jb.total;
+  return 0;
+}
+
+/* cpu/light.c:19's pow(fmax(x, 0.0), e) in long double: where the double pow
+ * of two libraries may round differently, this says how close the true value
+ * lies to a float rounding boundary.  Explains a mismatch; decides nothing. */
+long double oracle_spec_pow_ld(double x, double e)
+{
+  return powl(fmaxl((long double)x, 0.0L), (long double)e);
+}
+
+/* the same through memory: ctypes hands a long double result over as a double */
+void oracle_spec_pow_ld_to(double x, double e, long double *out) { *out = oracle_spec_pow_ld(x, e); }
+
 /* ---- loader: cpu/parser.c:4-116, cpu/parse_obj.c:3-92, cpu/stack.c ---- */
 
 /* The reference's vertex "stack" is a LIFO linked list (cpu/stack.c:23-47);

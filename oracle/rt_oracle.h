@@ -65,6 +65,20 @@ int oracle_render(const struct or_scene *scene, const int *pixels, size_t npix,
 int oracle_render_gpu(const struct or_scene *scene, const int *pixels, size_t npix,
                       int nthreads, unsigned char *out, struct or_counts *counts);
 
+/* trace(ray, 1.0) of cpu/raytracer.c:19-34 for n caller-supplied rays, the
+ * directions used as given: out_rgb receives n*3 floats; out_first (or NULL)
+ * each ray's first hit as collide() returns it (obj = -1, P = N = 0: none);
+ * counts as oracle_render's, max_depth over the batch. */
+struct or_first_hit { int obj; struct or_vec3 P, N; };
+int oracle_trace_rays(const struct or_scene *scene, const struct or_ray *rays, size_t n,
+                      int nthreads, float *out_rgb, struct or_first_hit *out_first,
+                      struct or_counts *counts);
+
+/* powl(fmaxl(x, 0), e): cpu/light.c:19's specular power in long double.  Only
+ * to explain a one-ulp difference between two double pow implementations. */
+long double oracle_spec_pow_ld(double x, double e);
+void oracle_spec_pow_ld_to(double x, double e, long double *out);
+
 /* Camera samples (cpu/raytracer.c:50-61) against one triangle each: for
  * i < n, the PPM pixels [row0, row0 + rows) x [col0, col0 + cols) (rects[4i ..
  * 4i + 3]) against tris[i]: out[2i] = samples cpu/hit.c:15-44 accepts,
