@@ -18,7 +18,8 @@ extern "C" {
 
 // The build's geometry (shared by the device build and the host survey): the
 // DIR grid's float axes and extent, the POINT cube map's side.  1 with err
-// filled: no grid (a zero directional vector, too many cells).
+// filled: no grid (a zero directional vector, a non-finite vector, too many
+// cells).
 int lb_derive_grid(const LBParams* in, rtl::LbGeom& p, RtLightBuf* out, uint64_t& ncell, char* err, size_t errlen) {
   using namespace rtl;
   std::memset(&p, 0, sizeof p);
@@ -35,6 +36,12 @@ int lb_derive_grid(const LBParams* in, rtl::LbGeom& p, RtLightBuf* out, uint64_t
   p.slack = in->slack;
   p.s1 = in->s1;
   p.dmax = in->dmax;
+  if (!(std::isfinite(in->lv[0]) && std::isfinite(in->lv[1]) && std::isfinite(in->lv[2]))) {
+    // an infinite direction would give a one-cell grid with NaN axes, a NaN
+    // position a NaN cell coordinate in the query (rt_lightbuf_cell.h)
+    snprintf(err, errlen, "light with a non-finite vector");
+    return 1;  // no buffer, like the zero vector
+  }
   if (in->kind == RT_LB_DIR) {
     // axes: w = normalize(-l.v) (the rays' direction), u, v completing it;
     // rounded to float once -- the build and the query use the same floats

@@ -405,6 +405,11 @@ extern "C" int rt_hip_probe_shadows(rt_hip_ctx* c, unsigned light, const float* 
     int rc = lbuf_prepare(c, s);
     if (rc) return rc;
     if (!c->d_lbuf) return rt_set_error(RT_EINVAL, "no light buffers (octree contexts with light buffers on)");
+    // a light whose build fell back to the walk has a zeroed descriptor: the
+    // probe's scan would read cell 0 of a start table that does not exist
+    if (light >= c->lb_host.size() || c->lb_host[light].kind == RT_LB_NONE)
+      return rt_set_error(RT_EINVAL, "light %u has no buffer (its queries walk): %s", light,
+                          c->info.lightbuf_fail_reason);
   }
   if (!c->d_tri_prim) return rt_set_error(RT_EINVAL, "no triangles");
   KParams p = scene_params(c);

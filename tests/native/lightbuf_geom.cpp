@@ -26,10 +26,26 @@
 //      (point light) listed in its second cell -- and is never `never`.
 //      Every accepted pair is checked, in both modes;
 //   4. the set is not vacuous (the thresholds at the end of run()).
+// A second pass puts every row of tests/light_edges_util.py's light table
+// (kRows; positions scaled by 5 to this box) in the lights' place, adds the
+// integer lattice of the box to the origins, and applies checks 1-3 to every
+// row; non-vacuity is per row: where the reference accepts pairs, at least
+// 1,000 accepted and at least 50 found through a cell (first and second cell
+// counted apart: around a light inside the geometry nearly every pair is a
+// global one); exactly 0 accepted under the tiny, denormal and huge
+// directions and the point lights 1e9 and 3e38 away; every triangle `never`
+// under the tiny and denormal directions in proven mode; and the zero vector
+// refused by lb_geom_host with its message.  The five point lights on the
+// lattice run once more over triangles on the lattice (the faces of the box in
+// squares of 4: edges and vertices exactly in the cube map's face boundaries
+// and on the origins).  A third pass: +-inf and NaN in one
+// component, both kinds of light, refused with a reason of their own (host
+// only: nothing of it goes near a device).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -191,8 +207,45 @@ struct Entry {
 
 static const int kRaysPerTri = 8;
 
+// What the reference's test gives for a row's shadow rays.
+enum Gives { kShadows, kNothing, kNoGrid };
+struct Row {
+  const char* name;  // tests/light_edges_util.py ROW_NAMES (tests/test_lightbuf_geom.py compares)
+  uint32_t type;
+  float v[3];  // geom_rows(): a direction as it is, a position times 5
+  Gives gives;
+  bool lattice;  // the table's on-the-lattice flag: run once more over the lattice triangles
+};
+static const Row kRows[] = {
+    {"dir 0 -1 0", 1u, {0.0f, -1.0f, 0.0f}, kShadows, false},
+    {"dir 1 0 0", 1u, {1.0f, 0.0f, 0.0f}, kShadows, false},
+    {"dir 0 1 0 from below", 1u, {0.0f, 1.0f, 0.0f}, kShadows, false},
+    {"dir -0 0 1", 1u, {-0.0f, 0.0f, 1.0f}, kShadows, false},
+    {"dir 1 1 0", 1u, {1.0f, 1.0f, 0.0f}, kShadows, false},
+    {"dir 1 -1 1", 1u, {1.0f, -1.0f, 1.0f}, kShadows, false},
+    {"dir 1 1e-8 0", 1u, {1.0f, 9.99999994e-09f, 0.0f}, kShadows, false},
+    {"dir 0.5 -0.25 0", 1u, {0.5f, -0.25f, 0.0f}, kShadows, false},
+    {"dir 1e-20 0 0", 1u, {9.99999968e-21f, 0.0f, 0.0f}, kNothing, false},
+    {"dir denormal", 1u, {3.00000065e-39f, 3.00000065e-39f, 0.0f}, kNothing, false},
+    {"dir 1e30", 1u, {1.00000002e+30f, -1.00000002e+30f, 1.00000002e+30f}, kNothing, false},
+    {"dir zero", 1u, {0.0f, 0.0f, 0.0f}, kNoGrid, false},
+    {"point lattice centre", 2u, {0.0f, 0.0f, 0.0f}, kShadows, true},
+    {"point wall vertex", 2u, {20.0f, 0.0f, 0.0f}, kShadows, true},
+    {"point wall plane", 2u, {20.0f, 30.0f, 0.0f}, kShadows, true},
+    {"point box corner", 2u, {-40.0f, -20.0f, -40.0f}, kShadows, true},
+    {"point inside the closed box", 2u, {10.0f, -10.0f, 10.0f}, kShadows, true},
+    {"point 1e6 0 0", 2u, {5000000.0f, 0.0f, 0.0f}, kShadows, false},
+    {"point 1e6 1e6 1e6", 2u, {5000000.0f, 5000000.0f, 5000000.0f}, kShadows, false},
+    {"point 0 1e9 0", 2u, {0.0f, 5e+09f, 0.0f}, kNothing, false},
+    {"point 3e38", 2u, {3.00000001e+38f, 3.00000001e+38f, 3.00000001e+38f}, kNothing, false},
+    {"point off the lattice", 2u, {20.0f, 40.0f, 60.0000038f}, kShadows, false},
+};
+
+static const char* g_tag = "row";  // what a row's lines start with: "row", or "lattice row" over the lattice triangles
+
 static void run(const std::vector<float4>& tri, const std::vector<rt_vec3>& origins, const float sc[3], float sr,
-                const float blo[3], const float bhi[3], uint32_t type, const float lv[3], int proven, uint32_t cell_mul) {
+                const float blo[3], const float bhi[3], uint32_t type, const float lv[3], int proven, uint32_t cell_mul,
+                const Row* row = nullptr) {
   using namespace rtl;
   const uint32_t nprim = (uint32_t)(tri.size() / 3);
   char err[256] = {0};
@@ -204,6 +257,12 @@ static void run(const std::vector<float4>& tri, const std::vector<rt_vec3>& orig
   RtLightBuf lb;
   uint64_t ncell = 0;
   const int gr = lb_geom_host(&lp, p, &lb, ncell, err, sizeof err);
+  if (row && row->gives == kNoGrid) {  // no grid: the light's queries walk
+    CHECK(gr == 1 && std::strcmp(err, "directional light with a zero vector") == 0 && lb.kind == RT_LB_NONE,
+          "%s: lb_geom_host %d '%s' kind %u", row->name, gr, err, lb.kind);
+    std::printf("%s %s | %s x%u: refused: %s\n", g_tag, row->name, proven ? "proven" : "slack", cell_mul, err);
+    return;
+  }
   CHECK(gr == 0, "lb_geom_host: %d %s", gr, err);
   if (gr) return;
   uint32_t ctr[RT_LBC_WORDS] = {};
@@ -341,11 +400,24 @@ static void run(const std::vector<float4>& tri, const std::vector<rt_vec3>& orig
   }
   CHECK(missed == 0, "%llu accepted pairs are not where the query looks", missed);
 
+  if (row) std::printf("%s %s | ", g_tag, row->name);
   std::printf("%s %s x%u: cells %llu entries %llu | accepted pairs %llu: global %llu, first cell %llu (%llu within a "
               "float step of the limit, nearest %.3g), second cell %llu | global %llu never %llu band %llu big %llu\n",
               type == 1 ? "dir" : "point", proven ? "proven" : "slack", cell_mul, (unsigned long long)ncell, entries,
               accepted, by_global, by_first, tight, (double)margin, by_second, n_global, n_never, n_band, n_big);
   // ---- 4. not vacuous
+  if (row) {  // per row
+    if (row->gives == kShadows) {
+      CHECK(accepted >= 1000, "%s: %llu accepted pairs", row->name, accepted);
+      CHECK(by_first + by_second >= 50, "%s: %llu + %llu pairs found through a cell", row->name, by_first, by_second);
+    } else {
+      CHECK(accepted == 0, "%s: %llu accepted pairs where the reference accepts none", row->name, accepted);
+      // |a| <= |d| |e1 x e2| stays below 1e-7 for every triangle of the box
+      if (proven && type == 1 && p.dlen < 1e-15)
+        CHECK(n_never == nprim, "%s: %llu of %u triangles never", row->name, n_never, nprim);
+    }
+    return;
+  }
   CHECK(accepted >= 1000, "%llu accepted pairs", accepted);
   if (proven && type == 1) CHECK(n_never >= 1, "no triangle is never accepted");
   if (proven && type == 2) CHECK(n_band >= 1, "no band triangle");
@@ -392,6 +464,80 @@ int main() {
   for (uint32_t type = 1; type <= 2; type++)
     for (int proven = 0; proven <= 1; proven++)
       for (uint32_t mul : {1u, 16u}) run(tri, origins, sc, sr, blo, bhi, type, type == 1 ? kDirLight : kPointLight, proven, mul);
+  // ---- the light table: the same origins and the box's integer lattice (11^3 points, 4 apart)
+  std::vector<rt_vec3> more = origins;
+  for (int i = -5; i <= 5; i++)
+    for (int j = -5; j <= 5; j++)
+      for (int k = -5; k <= 5; k++) more.push_back(rt_vec3{4.0f * i, 4.0f * j, 4.0f * k});
+  for (const Row& r : kRows) {
+    std::printf("row %s | v = %.9g %.9g %.9g\n", r.name, (double)r.v[0], (double)r.v[1], (double)r.v[2]);
+    for (int proven = 0; proven <= 1; proven++)
+      for (uint32_t mul : {1u, 16u}) run(tri, more, sc, sr, blo, bhi, r.type, r.v, proven, mul, &r);
+  }
+  // ---- the point lights on the lattice over triangles on the lattice: the faces of the box
+  // [-20, 20]^3 in squares of 4, the diagonals alternating (1,200 triangles), and the lattice origins
+  // alone.  Edges and vertices lie exactly in the cube map's face boundaries |x| == |y| and on the
+  // origins themselves, which the generated triangles above never do.
+  {
+    std::vector<float4> lat;
+    for (int a = 0; a < 3; a++)
+      for (int side = -1; side <= 1; side += 2)
+        for (int i = 0; i < 10; i++)
+          for (int j = 0; j < 10; j++) {
+            const int b = (a + 1) % 3, c = (a + 2) % 3;
+            double q[4][3];
+            for (int k = 0; k < 4; k++) {
+              q[k][a] = 20.0 * side;
+              q[k][b] = -20.0 + 4.0 * (i + (k == 1 || k == 2));
+              q[k][c] = -20.0 + 4.0 * (j + (k >= 2));
+            }
+            const int t[2][2][3] = {{{0, 1, 2}, {0, 2, 3}}, {{0, 1, 3}, {1, 2, 3}}};
+            for (int h = 0; h < 2; h++) {
+              const int* w = t[(i + j) & 1][h];
+              double e1[3], e2[3];
+              for (int k = 0; k < 3; k++) {
+                e1[k] = q[w[1]][k] - q[w[0]][k];
+                e2[k] = q[w[2]][k] - q[w[0]][k];
+              }
+              push(lat, q[w[0]], e1, e2);
+            }
+          }
+    const float c0[3] = {0.0f, 0.0f, 0.0f}, lo[3] = {-20.0f, -20.0f, -20.0f}, hi[3] = {20.0f, 20.0f, 20.0f};
+    const std::vector<rt_vec3> lattice(more.begin() + (long)origins.size(), more.end());
+    g_tag = "lattice row";
+    for (const Row& r : kRows)
+      if (r.lattice)
+        for (int proven = 0; proven <= 1; proven++)
+          for (uint32_t mul : {1u, 16u}) run(lat, lattice, c0, 20.0f, lo, hi, r.type, r.v, proven, mul, &r);
+    g_tag = "row";
+  }
+  // ---- non-finite vectors: refused before any grid or cell is derived from them
+  {
+    const float bad[3] = {__builtin_inff(), -__builtin_inff(), __builtin_nanf("")};
+    unsigned refused = 0;
+    for (uint32_t type = 1; type <= 2; type++)
+      for (int a = 0; a < 3; a++)
+        for (float b : bad)
+          for (int proven = 0; proven <= 1; proven++) {
+            float lv[3] = {type == 1 ? kDirLight[0] : kPointLight[0], type == 1 ? kDirLight[1] : kPointLight[1],
+                           type == 1 ? kDirLight[2] : kPointLight[2]};
+            lv[a] = b;
+            char err[256] = {0};
+            LBParams lp;
+            lb_fill(lp, sc, sr, blo, bhi, 64.0f, type, lv, nprim, proven);
+            lp.tri = tri.data();
+            HostBP p{};
+            RtLightBuf lb;
+            uint64_t ncell = 0;
+            const int gr = lb_geom_host(&lp, p, &lb, ncell, err, sizeof err);
+            CHECK(gr == 1 && std::strcmp(err, "light with a non-finite vector") == 0 && lb.kind == RT_LB_NONE,
+                  "type %u component %d = %g: lb_geom_host %d '%s' kind %u", type, a, (double)b, gr, err, lb.kind);
+            unsigned long long sv[RT_LBS_WORDS];
+            CHECK(rt_lightbuf_survey_host(&lp, 1, sv, err, sizeof err) == -1, "the survey of a non-finite light");
+            refused += gr == 1;
+          }
+    std::printf("non-finite vectors: %u of 36 refused\n", refused);
+  }
   if (failures) {
     std::printf("%d failures\n", failures);
     return 1;
