@@ -613,6 +613,62 @@ int rt_hip_ao_rays_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n, 
                         unsigned k, const float *h_table, unsigned m, unsigned seed, float *h_origins,
                         float *h_dirs, unsigned char *h_shot /* may be NULL */);
 
+/* Direct light for caller's surface records (new): for each of n rt_gsample
+ * records in device memory (8-byte aligned; a rank's tile buffer straight from
+ * rt_hip_gbuffer, the assembled samples, a ray batch's records, or points of
+ * the caller's own: lightmap texels, probes in free space), d_rgb[3 i ..]
+ * receives the three float channels of
+ *     apply_light(scene, objects[obj_i], (P_i, N_i))      (cpu/light.c:33-100)
+ * under the context's current lights and materials (rt_hip_set_lights,
+ * rt_hip_set_materials): the lights summed in file order with the reference's
+ * colour algebra, N used as given (not normalised), no coef, no reflection.
+ * The specular term needs no view direction (cpu/light.c:7-22).  d_lit[i], if
+ * d_lit is not NULL, receives the unshadowed mask in the sense of a relight:
+ * bit li (li < 32) is set iff light li is directional or point and
+ * collide_dist of its shadow ray from P_i (cpu/light.c:51-54, 76-80) is 0.
+ * Lights from index 32 up count in the colour and have no bit.
+ *
+ * A record shades iff prim >= 0, 0 <= obj < the context's object count, every
+ * component of P and N is finite and N is not zero by vector3_is_zero
+ * (csrc/rt_dlight_items.h is the one statement, rtgpu.direct_light_shades its
+ * numpy twin).  Every other record -- a miss, the G-buffer's zero-normal
+ * winner, a non-finite point -- gets colour 0 0 0 and mask 0.  Every output
+ * word of [0, n) is written exactly once, nothing past it; the outputs need no
+ * clearing.
+ *
+ * Every shadow decision is has_direct_hit (cpu/light.c:24-31); the route only
+ * decides how it is found.  FLAT: brute force.  Octree: through the light's
+ * buffer when it has one and P lies in the buffer's proof box (proven in the
+ * default exact-shadow mode); otherwise -- P off the box, the build failed,
+ * rt_hip_set_light_buffers off -- by the walk of an occlusion batch without a
+ * distance bound (tested at the default culling slack; proven under
+ * rt_hip_set_exact_reflections for directions within that walk's bound, a
+ * longer walked ray -- most point lights' -- is counted in closest_unproven
+ * and rt_hip_stats reports RT_EINEXACT, as for an occlusion batch).  Nothing
+ * is deferred.  Unlike a batch, a
+ * shadow ray with a zero or huge direction (a light at P, a zero light vector,
+ * a light 3e38 away) is asked like any other, as the reference asks it.
+ * RT_RAYS_PACKET: the 64 records of a work item walk one light's rays as a
+ * packet; the same bytes.
+ *
+ * To the context the call is an occlusion batch: it writes no hit record, the
+ * kept frame survives it, rt_hip_frame_check counts renders only, and
+ * rt_hip_stats directly after reads camera = records that shaded, shadow =
+ * queries asked, shadow_deferred = queries of lights with a buffer that left
+ * its proof box and walked, shadow_zero_risk, closest_unproven and
+ * depth_overflow as counted, shadow_unproven and every other counter 0.
+ * Asynchronous on `stream`.  RT_EINVAL with nothing changed: a NULL context;
+ * NULL samples or d_rgb with n > 0; samples not 8-byte aligned; n >
+ * RT_RAYS_MAX; flags other than RT_RAYS_PACKET; a non-default traversal
+ * policy; rt_hip_set_count_work; a context left broken by a failed geometry
+ * update.  n == 0 returns RT_OK and writes nothing. */
+int rt_hip_direct_light(rt_hip_ctx *ctx, const void *d_samples, size_t n, unsigned flags,
+                        float *d_rgb, unsigned *d_lit /* may be NULL */, void *stream);
+/* Upload, rt_hip_direct_light on the context's stream, download, rt_hip_stats;
+ * synchronous. */
+int rt_hip_direct_light_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n, unsigned flags,
+                             float *h_rgb, unsigned *h_lit /* may be NULL */, rt_stats *stats);
+
 /* gpu/rt compatibility mode (gpu/raytracer.cu:31-129,
  * gpu/light.cu, gpu/colors.cu): the camera's frame rendered at 3x width and
  * height with one ray per high-resolution pixel, uint8 saturating colours,

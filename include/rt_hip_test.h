@@ -137,6 +137,13 @@ int rt_hip_set_lightbuf_entry_cap(rt_hip_ctx *ctx, unsigned long long cap);
  * triangles with more than 1024, [10] with 65..1024, [11] triangles with more than 64. */
 int rt_lightbuf_survey(const rt_scene *scene, unsigned light, int exact, unsigned stride,
                        unsigned long long out[12]);
+/* The proof box of light `light`'s buffer as the context holds it (floats
+ * inside the build's origin box, csrc/rt_lightbuf.h RtLightBuf::olo, ohi): the
+ * shadow query of rt_hip_direct_light from a point inside it goes through the
+ * buffer.  *has = 0 (and the boxes untouched): the light has no buffer -- not
+ * a casting light, its build failed, the buffers are off or not built yet, a
+ * FLAT context. */
+int rt_hip_lightbuf_box(rt_hip_ctx *ctx, unsigned light, int *has, float lo[3], float hi[3]);
 /* Shadow-query probe (tests, tools): light `light`'s shadow ray
  * (cpu/light.c:53,78) from each of n origins (x, y, z floats), answered
  * through the context's light buffer (brute = 0) or by brute force over every

@@ -181,6 +181,7 @@ struct rt_hip_ctx {
   DevBuf<unsigned long long> d_occl_stats;
   int occl_grid = 0;                // the kernel's persistent grid (0: not asked yet)
   int ao_grid[2] = {0, 0};          // ao_kernel's, k <= 64 and k > 64 (csrc/rt_ao.cpp)
+  int dlight_grid = 0;              // dlight_kernel's (csrc/rt_dlight.cpp)
   int last_occl = 0;
   hipStream_t occl_stream = nullptr;
   KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here

@@ -262,6 +262,18 @@ struct AoArgs {
   unsigned char* shot;      // ao_rays_kernel: one byte per sample, or NULL
 };
 
+// What the direct-light kernel takes beside the KParams (csrc/rt_dlight.h):
+// records in, three colour words and (optionally) one mask word per record out.
+struct DlArgs {
+  const uint2* samples;  // n rt_gsample records as five 8-byte pairs each
+  unsigned long long n;  // records
+  uint32_t nitems;       // rt_ray_item_count(n)
+  uint32_t walk;         // RT_RAYS_WALK_*, as OcclArgs::walk: the walk off a light buffer's proof box
+  uint32_t nobj;         // objects of the context: rows of KParams::mshade
+  float* rgb;            // 3 floats per record
+  uint32_t* lit;         // one word per record, or NULL
+};
+
 // The three launches of one render (policy = RT_POLICY_*, octree only):
 // trace (closest hits -> hit records), shade (shadow queries + Phong per
 // record -> terms), fold (terms -> the rank's tile buffer)
@@ -319,6 +331,10 @@ extern "C" hipError_t rt_occl_grid(int accel, int cus, int* grid);
 extern "C" hipError_t rt_launch_ao(const KParams* p, const AoArgs* a, int accel, int grid, hipStream_t stream);
 extern "C" hipError_t rt_ao_grid(int accel, int wide, int cus, int* grid);  // wide: k > 64
 extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream);
+// Direct light for records (csrc/rt_dlight.h): its one kernel, one-wave
+// workgroups pulling items of 64 records, and that kernel's persistent grid
+extern "C" hipError_t rt_launch_dlight(const KParams* p, const DlArgs* a, int accel, int grid, hipStream_t stream);
+extern "C" hipError_t rt_dlight_grid(int accel, int cus, int* grid);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

@@ -96,6 +96,9 @@ int occl_stats(rt_hip_ctx* c, rt_stats* out) {
   out->depth_overflow = h[RT_ST_DEPTH_OVERFLOW];
   out->shadow_zero_risk = h[RT_ST_SHADOW_ZERO_RISK];
   out->closest_unproven = h[RT_ST_CLOSEST_UNPROVEN];
+  // direct light for records (csrc/rt_dlight.h) counts its queries off a light buffer's proof box in the
+  // hits' slot, which no walk of a batch adds to: 0 after every other batch
+  out->shadow_deferred = h[RT_ST_HITS];
   if (out->depth_overflow)
     return rt_set_error(RT_EDEPTH, "%llu occlusion queries overflowed a traversal stack", out->depth_overflow);
   if (out->shadow_zero_risk)

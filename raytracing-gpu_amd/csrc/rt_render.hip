@@ -772,7 +772,8 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
 #include "rt_shade_tables.h"  // shade_tables_kernel: after those
 #include "rt_rays.h"  // the ray batches' kernels: after those
 #include "rt_occl.h"  // the occlusion batches' kernel: after those
-#include "rt_ao.h"  // ambient occlusion from records: last
+#include "rt_ao.h"  // ambient occlusion from records: after those
+#include "rt_dlight.h"  // direct light for records: last
 
 // ---------------------------------------------------------------- launchers
 // One instantiation per (kernel, accel, work counting, policy); the default
@@ -1063,4 +1064,27 @@ extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream) {
   if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
   hipLaunchKernelGGL((rt::ao_rays_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *a);
   return hipGetLastError();
+}
+
+// Direct light for records (rt_kernels.h, csrc/rt_dlight.h).  Last, for the
+// same reason yet again: every earlier kernel keeps its place.
+static const void* dlight_kernel_of(int accel) {
+  return accel == RT_ACCEL_FLAT_D ? (const void*)rt::dlight_kernel<RT_ACCEL_FLAT_D>
+                                  : (const void*)rt::dlight_kernel<RT_ACCEL_OCTREE_D>;
+}
+
+extern "C" hipError_t rt_dlight_grid(int accel, int cus, int* grid) {
+  int per_cu = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dlight_kernel_of(accel), 64, 0);
+  if (e != hipSuccess) return e;
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 32) per_cu = 32;
+  *grid = per_cu * cus;
+  return hipSuccess;
+}
+
+extern "C" hipError_t rt_launch_dlight(const KParams* p, const DlArgs* a, int accel, int grid, hipStream_t stream) {
+  if (grid <= 0) return hipErrorInvalidValue;
+  void* args[] = {(void*)p, (void*)a};
+  return hipLaunchKernel(dlight_kernel_of(accel), dim3(grid), dim3(64), args, 0, stream);
 }

@@ -241,6 +241,12 @@ _PROTOS = [
                                  C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_ao_rays_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p,
                                       C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_direct_light", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    ("rt_hip_direct_light_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
+                                           C.POINTER(Stats)]),
+    ("rt_hip_lightbuf_box", C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float)]),
     ("rt_hip_malloc", C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("rt_hip_free", C.c_int, [C.c_void_p]),
     ("rt_hip_memcpy_d2h", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -837,6 +843,73 @@ def ao_open_share(counts, samples, k):
     return 1.0 - c / float(k)
 
 
+# ---- direct light for caller's records (include/rt_hip.h rt_hip_direct_light) ----
+def records_from_points(P, N, obj, prim=0):
+    """GSAMPLE records for Context.direct_light from caller points: (n, 3)
+    positions and normals (used as given, not normalised), an object index
+    (scalar or (n,): whose material shades the point) and a prim (>= 0: a hit;
+    the direct light reads only its sign).  queries = 0, dist = 0."""
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    N = np.ascontiguousarray(N, dtype=np.float32).reshape(-1, 3)
+    assert len(P) == len(N)
+    r = np.zeros(len(P), GSAMPLE)
+    r["P"], r["N"] = P, N
+    r["obj"] = np.broadcast_to(np.asarray(obj, dtype=np.int32), (len(P),))
+    r["prim"] = np.broadcast_to(np.asarray(prim, dtype=np.int32), (len(P),))
+    return r
+
+
+def direct_light_shades(records, nobjects):
+    """Which GSAMPLE records Context.direct_light shades (csrc/rt_dlight_items.h
+    rt_dl_shades): a hit (prim >= 0) of an object 0 <= obj < nobjects whose P
+    and N are finite and whose N is not zero by vector3_is_zero (-0.0 is zero,
+    a denormal is not) -> bool (n,).  Every other record gets 0 0 0 and mask 0."""
+    r = np.ascontiguousarray(records, dtype=GSAMPLE).reshape(-1)
+    pb, nb = r["P"].view(np.uint32), r["N"].view(np.uint32)
+    fin = ((pb & 0x7f800000) != 0x7f800000).all(axis=1) & ((nb & 0x7f800000) != 0x7f800000).all(axis=1)
+    zero = ((nb[:, 0] | nb[:, 1] | nb[:, 2]) & 0x7fffffff) == 0
+    return (r["prim"] >= 0) & (r["obj"] >= 0) & (r["obj"] < int(nobjects)) & fin & ~zero
+
+
+def _light_rows(lights):
+    """(type, (x, y, z) float32) per light of a ctypes Light array or a
+    sequence of (type, r, g, b, x, y, z)."""
+    rows = []
+    for l in lights:
+        if isinstance(l, Light):
+            rows.append((int(l.type), np.array([l.v.x, l.v.y, l.v.z], np.float32)))
+        else:
+            rows.append((int(l[0]), np.array(l[4:7], np.float32)))
+    return rows
+
+
+def shadow_rays_host(records, lights):
+    """The shadow rays Context.direct_light decides, in float32 numpy: per
+    casting light (type 1 directional, 2 point) of `lights`, in their order
+    (casting_lights gives their indices), a tuple (origins, dirs) of (n, 3)
+    float32 arrays in the operation order of cpu/light.c:53,78 -- origin P, direction
+    vector3_scale(l.v, -1) for a directional light, vector3_sub(l.v, P) for a
+    point light; neither is normalised."""
+    r = np.ascontiguousarray(records, dtype=GSAMPLE).reshape(-1)
+    P = np.ascontiguousarray(r["P"], dtype=np.float32)
+    out = []
+    for t, v in _light_rows(lights):
+        if t == 1:
+            d = np.broadcast_to(v * np.float32(-1.0), P.shape).astype(np.float32)
+        elif t == 2:
+            with np.errstate(all="ignore"):
+                d = (v[None, :] - P).astype(np.float32)
+        else:
+            continue
+        out.append((P.copy(), np.ascontiguousarray(d)))
+    return out
+
+
+def casting_lights(lights):
+    """Indices of the lights that cast a shadow ray (directional and point)."""
+    return [li for li, (t, _) in enumerate(_light_rows(lights)) if t in (1, 2)]
+
+
 class Context:
     """One device image of a scene (rt_hip_create); renders through the C ABI."""
 
@@ -1310,6 +1383,41 @@ class Context:
             RT_RAYS_PACKET if packet else 0, out.ctypes.data_as(C.c_void_p), C.byref(st))),
             "rt_hip_ambient_occlusion_host")
         return out, st.as_dict()
+
+    def direct_light_device(self, d_samples, n, d_rgb, d_lit=0, packet=False, stream=None):
+        """rt_hip_direct_light on device pointers (asynchronous): d_samples = n
+        GSAMPLE records (a tile buffer, assembled samples, a ray batch's
+        records, caller points), d_rgb receives 3 n floats, d_lit (0: none) n
+        uint32 unshadowed-light masks."""
+        _check(lib().rt_hip_direct_light(self.h, C.c_void_p(d_samples) if d_samples else None, int(n),
+                                         RT_RAYS_PACKET if packet else 0, C.c_void_p(d_rgb) if d_rgb else None,
+                                         C.c_void_p(d_lit) if d_lit else None,
+                                         C.c_void_p(stream) if stream else None), "rt_hip_direct_light")
+
+    def direct_light(self, samples, packet=False, lit=False):
+        """apply_light of cpu/light.c:33-100 at each GSAMPLE record's (P, N)
+        with its object's material, under the context's current lights
+        (rt_hip_direct_light_host) -> (rgb (n, 3) float32, uint32 (n,) masks of
+        the unshadowed casting lights 0..31 or None, stats).  Records that do
+        not shade (direct_light_shades) get 0 0 0 and mask 0."""
+        smp = np.ascontiguousarray(samples, dtype=GSAMPLE).reshape(-1)
+        rgb = np.zeros((len(smp), 3), np.float32)
+        mask = np.zeros(len(smp), np.uint32) if lit else None
+        st = Stats()
+        self.last_rc = 0  # the call's return code (RT_EINEXACT passes _check_render after a parity-breaking knob)
+        self._check_render(self._keep_rc(lib().rt_hip_direct_light_host(
+            self.h, smp.ctypes.data_as(C.c_void_p), len(smp), RT_RAYS_PACKET if packet else 0,
+            rgb.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p) if lit else None, C.byref(st))),
+            "rt_hip_direct_light_host")
+        return rgb, mask, st.as_dict()
+
+    def lightbuf_box(self, light):
+        """The proof box (lo, hi), float32 (3,) each, of light `light`'s
+        buffer (rt_hip_lightbuf_box), or None when the light has none."""
+        has = C.c_int(0)
+        lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
+        _check(lib().rt_hip_lightbuf_box(self.h, int(light), C.byref(has), lo, hi), "rt_hip_lightbuf_box")
+        return (np.array(lo[:], np.float32), np.array(hi[:], np.float32)) if has.value else None
 
     def ao_rays_device(self, d_samples, n, k, d_table, m, seed, d_origins, d_dirs, d_shot=0, base=0, stream=None):
         """rt_hip_ao_rays on device pointers (asynchronous)."""
