@@ -1,12 +1,10 @@
 // rt_ao.cpp -- host side of ambient occlusion from G-buffer records
 // (include/rt_hip.h rt_hip_ambient_occlusion, rt_hip_ambient_occlusion_host,
 // rt_hip_ao_rays, rt_hip_ao_rays_host): the refusals, the fused kernel's launch (csrc/rt_ao.h) and
-// the generator's.  To the context a call is an occlusion batch
-// (csrc/rt_occl.cpp): it counts into the batches' stats block, sets last_occl,
-// uses the stack spill area and the item counters in stream order, and leaves
-// the kept frame, the lists, the overlap state and the render's counters as
-// they are.  The ray rule and the items: csrc/rt_ao_items.h.
-#include "rt_ctx.h"
+// the generator's.  To the context a counting call is a batch of the one host
+// path (csrc/rt_batch.h), which says what it uses and what it leaves as it is.
+// The ray rule and the items: csrc/rt_ao_items.h.
+#include "rt_batch.h"
 #include "rt_ao_items.h"
 
 static_assert(RT_AO_KMAX == RT_AO_KMAX_D, "include/rt_hip.h and csrc/rt_ao_items.h disagree on k's limit");
@@ -14,8 +12,7 @@ static_assert(RT_AO_KMAX == RT_AO_KMAX_D, "include/rt_hip.h and csrc/rt_ao_items
 // What the three entry points refuse alike, by the sizes alone; nothing of the
 // context has changed when a refusal returns.
 static int ao_refuse(const rt_hip_ctx* c, size_t n, unsigned k, unsigned m) {
-  if (!c) return rt_set_error(RT_EINVAL, "null context");
-  RT_CTX_LIVE(c);
+  if (int rc = batch_refuse_ctx(c)) return rc;
   if (k == 0 || k > RT_AO_KMAX) return rt_set_error(RT_EINVAL, "%u rays per sample: 1 to %u", k, (unsigned)RT_AO_KMAX);
   if (m == 0) return rt_set_error(RT_EINVAL, "an empty direction table");
   if (n > RT_RAYS_MAX / k)
@@ -29,14 +26,6 @@ static int ao_refuse(const rt_hip_ctx* c, size_t n, unsigned k, unsigned m) {
 static int ao_refuse_ptrs(const void* d_samples, size_t n, const float* d_table) {
   if (n && (!d_samples || !d_table)) return rt_set_error(RT_EINVAL, "null samples or table");
   if ((uintptr_t)d_samples & 7u) return rt_set_error(RT_EINVAL, "samples must be 8-byte aligned");
-  return RT_OK;
-}
-// ... and what the counting call refuses beside them, as an occlusion batch does
-static int ao_refuse_batch(const rt_hip_ctx* c, unsigned flags) {
-  if (flags & ~RT_RAYS_PACKET) return rt_set_error(RT_EINVAL, "unknown ambient occlusion flags %#x", flags);
-  if (c->policy != RT_POLICY_DEFAULT)
-    return rt_set_error(RT_EINVAL, "ambient occlusion needs the default traversal policy (have %d)", c->policy);
-  if (c->count_work) return rt_set_error(RT_EINVAL, "ambient occlusion cannot run as the work-counting pass");
   return RT_OK;
 }
 
@@ -63,51 +52,18 @@ extern "C" int rt_hip_ambient_occlusion(rt_hip_ctx* c, const void* d_samples, si
   int rc = ao_refuse(c, n, k, m);
   if (!rc) rc = ao_refuse_ptrs(d_samples, n, d_table);
   if (!rc && n && !d_occluded) rc = rt_set_error(RT_EINVAL, "null occlusion output");
-  if (!rc) rc = ao_refuse_batch(c, flags);
+  if (!rc) rc = batch_refuse_mode(c, flags, "", "ambient occlusion");
   if (rc || n == 0) return rc;
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  // an empty octree scene has nothing to traverse: the FLAT kernel with 0 records
-  const bool empty = c->accel == RT_ACCEL_OCTREE && !c->d_node;
-  const int dacc = (c->accel == RT_ACCEL_FLAT || empty) ? RT_ACCEL_FLAT_D : RT_ACCEL_OCTREE_D;
-  const bool octree = dacc == RT_ACCEL_OCTREE_D;
-  KParams p = scene_params(c);
   AoArgs a = ao_args(d_samples, n, base, k, d_table, m, seed);
   a.tmax = tmax;
   a.out = d_occluded;
-  if (octree && c->exact_refl) {  // the proven closest walk and its bounds
-    if ((rc = reflect_prepare(c, s))) return rc;
-    p.node_rf = c->d_node_rf;
-    a.walk = RT_RAYS_WALK_EXACT;
-  } else if (octree && (flags & RT_RAYS_PACKET)) {
-    a.walk = RT_RAYS_WALK_PACKET;
-  }
-  // the batches' stats block and this kernel's own grid
-  if (!c->d_occl_stats) HIP_TRY(c->d_occl_stats.alloc(RT_STAT_SETS * RT_STAT_STRIDE));
-  const int wide = k > 64;  // its own kernel (csrc/rt_ao.h)
-  if (!c->ao_grid[wide]) {
-    int g = 0;
-    HIP_TRY(rt_ao_grid(dacc, wide, c->cus, &g));
-    c->ao_grid[wide] = g;
-  }
-  int grid = c->ao_grid[wide];
-  // the spill area holds [entry][lane] for so many one-wave workgroups
-  if (octree) grid = (int)std::min<size_t>((size_t)grid, c->d_spill.cap() / ((size_t)64 * RT_SPILL_STACK));
-  if ((long long)a.nitems < grid) grid = (int)a.nitems;
-  p.tile_counter = c->d_counter;
-  p.stats = c->d_occl_stats;
-  // every device pointer the kernel follows must exist (a null one would
-  // fault the card, not fail the call)
-  if (!p.tile_counter || !p.stats || grid <= 0 || (p.nrec && !p.tri))
-    return rt_set_error(RT_EHIP, "ambient occlusion: device buffers missing");
-  if (octree && (!p.node || !p.spill || !p.tri || ((a.walk & RT_RAYS_WALK_EXACT) && (!p.node_rf || !p.tri_prim))))
+  BatchLaunch b;
+  const int kind = k > 64 ? RT_BATCH_AO_WIDE : RT_BATCH_AO;  // k > 64: its own kernel (csrc/rt_ao.h)
+  if ((rc = batch_begin(c, stream, flags, kind, a.nitems, false, "ambient occlusion", &b))) return rc;
+  a.walk = b.walk;
+  if ((a.walk & RT_RAYS_WALK_EXACT) && !b.p.tri_prim)  // the winner's flag is read from its prim-order record
     return rt_set_error(RT_EHIP, "ambient occlusion: octree buffers missing");
-  HIP_TRY(hipMemsetAsync(c->d_counter, 0, kItemCounterBytes, s));
-  HIP_TRY(hipMemsetAsync(c->d_occl_stats, 0, kStatBytes, s));
-  HIP_TRY(rt_launch_ao(&p, &a, dacc, grid, s));
-  c->last_occl = 1;  // what rt_hip_stats reads next
-  c->occl_stream = s;
-  return RT_OK;
+  return batch_run(c, b, &a);
 }
 
 extern "C" int rt_hip_ao_rays(rt_hip_ctx* c, const void* d_samples, size_t n, unsigned long long base, unsigned k,
@@ -158,12 +114,9 @@ extern "C" int rt_hip_ambient_occlusion_host(rt_hip_ctx* c, const rt_gsample* h_
                                              rt_stats* st) {
   int rc = ao_refuse(c, n, k, m);
   if (!rc && n && (!h_samples || !h_table || !h_occluded)) rc = rt_set_error(RT_EINVAL, "null samples, table or output");
-  if (!rc) rc = ao_refuse_batch(c, flags);
+  if (!rc) rc = batch_refuse_mode(c, flags, "", "ambient occlusion");
   if (rc) return rc;
-  if (n == 0) {  // nothing launched, nothing written
-    if (st) std::memset(st, 0, sizeof *st);
-    return RT_OK;
-  }
+  if (n == 0) return batch_host_none(st);
   HIP_TRY(hipSetDevice(c->device));
   DevBuf<rt_gsample> d_s;
   DevBuf<float> d_t;
@@ -173,11 +126,8 @@ extern "C" int rt_hip_ambient_occlusion_host(rt_hip_ctx* c, const rt_gsample* h_
   hipStream_t s = c->stream;
   HIP_TRY(hipMemcpyAsync(d_s, h_samples, n * sizeof(rt_gsample), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_t, h_table, 3 * (size_t)m * sizeof(float), hipMemcpyHostToDevice, s));
-  rt_stats tmp;
   rc = rt_hip_ambient_occlusion(c, d_s.get(), n, base, k, d_t.get(), m, seed, tmax, flags, d_out.get(), nullptr);
   if (!rc && hipMemcpyAsync(h_occluded, d_out, n * sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess)
     rc = rt_set_error(RT_EHIP, "D2H occlusion counts");
-  if (!rc) rc = rt_hip_stats(c, st ? st : &tmp);  // (synchronises)
-  (void)hipStreamSynchronize(s);                  // the buffers above go
-  return rc;
+  return batch_host_end(c, rc, st);
 }

@@ -50,19 +50,9 @@ __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void ao_kernel(KParams p, A
   WorkCount wc = {};
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : kStackArea];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : kStageOct];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   // the lane's place in every item (worked out per item: a multiply and a
   // shift, rt_ao_lane_sample): sample lq of the item, and of that sample's
   // round ray lane - lq k; a lane from spi k up has no ray (k <= 64)

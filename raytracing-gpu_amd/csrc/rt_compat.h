@@ -104,19 +104,9 @@ __global__ __launch_bounds__(64, RT_MIN_WAVES) void compat_kernel(KParams p) {
   WorkCount wc = {};
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : kStackArea];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : kStageOct];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   uint32_t* img = (uint32_t*)p.out;
   for (;;) {
     uint32_t t = 0;
@@ -139,13 +129,7 @@ __global__ __launch_bounds__(64, RT_MIN_WAVES) void compat_kernel(KParams p) {
       if (am == 0) break;
       wc.closest += (uint32_t)__popcll(am);
       Ray r = make_ray(p, o, d, depth == 0 ? p.eps_rel_cam : p.eps_rel);
-      Best b;
-      b.dist = __builtin_inff();
-      b.t_cut = __builtin_inff();
-      b.prim = 0xffffffffu;
-      b.obj = 0;
-      b.u = b.v = 0.0f;
-      b.t = 0.0f;
+      Best b = best_none();
       closest_q<ACCEL, false, POL>(p, r, alive, depth, b, stk, w, wc);
       // the camera rays' candidate lists (rt_hip_render_compat builds them for
       // this frame's sample model): the same exactness as cpu mode

@@ -10,8 +10,10 @@
 //   rt_verify.cpp  probes, verification, timing and measurement hooks
 //   rt_multi.cpp   rt_raytrace_multi: N GPUs, RCCL exchange and gather
 //   rt_rays.cpp    rt_hip_trace_rays, rt_hip_frame_rays: a caller's ray batches
+//   rt_batch.cpp   what the next three share: refusals, one launch path, their stats (rt_batch.h)
 //   rt_occl.cpp    rt_hip_occluded: a caller's occlusion batches
 //   rt_ao.cpp      rt_hip_ambient_occlusion: occlusion counts per G-buffer record
+//   rt_dlight.cpp  rt_hip_direct_light: direct light per G-buffer record
 // Internal, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -173,15 +175,13 @@ struct rt_hip_ctx {
   int lb_proven = -1;               // built proven (exact_shadows) or slack-grown
   unsigned long long lb_entry_cap = 0;  // test hook: fail builds past this many entries (0: none)
   int last_batch = 0;               // the last launch was a ray batch (rt_hip_trace_rays): rt_hip_stats reports rays, no list
-  // occlusion batches (rt_hip_occluded, csrc/rt_occl.cpp) count into a stats
+  // occlusion batches and their kin (csrc/rt_batch.h) count into a stats
   // block of their own (the layout of d_stats): the render's trace-side
   // counters, which a relight keeps, stay as they are.  last_occl: the last
   // operation was such a batch, on occl_stream -- rt_hip_stats reads this
   // block then; every render, relight, ray batch and compat render clears it
   DevBuf<unsigned long long> d_occl_stats;
-  int occl_grid = 0;                // the kernel's persistent grid (0: not asked yet)
-  int ao_grid[2] = {0, 0};          // ao_kernel's, k <= 64 and k > 64 (csrc/rt_ao.cpp)
-  int dlight_grid = 0;              // dlight_kernel's (csrc/rt_dlight.cpp)
+  int batch_grid[RT_NBATCH][2] = {};  // [RT_BATCH_*][RT_ACCEL_*_D]: the kernel's persistent grid (0: not asked yet)
   int last_occl = 0;
   hipStream_t occl_stream = nullptr;
   KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here
@@ -393,5 +393,5 @@ int choose_accel(const rt_scene* s);                                            
 int cand_prepare(rt_hip_ctx* c, const rt_frame* f, KParams* kp, hipStream_t s, int compat = 0,
                  bool from_render = false);  // rt_lists.cpp
 unsigned long long* cost_sum_of(rt_hip_ctx* c);                                    // rt_lists.cpp
-int occl_stats(rt_hip_ctx* c, rt_stats* out);                                      // rt_occl.cpp
+int occl_stats(rt_hip_ctx* c, rt_stats* out);                                      // rt_batch.cpp
 

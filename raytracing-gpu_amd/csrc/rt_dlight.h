@@ -44,27 +44,7 @@ __device__ __forceinline__ bool dlight_q(const KParams& p, const Ray& r, bool ac
                                          WaveCtx& w, WorkCount& wc) {
   const OcclBound ob{__builtin_inff(), __builtin_inff()};
   if (ACCEL == RT_ACCEL_FLAT_D) return use_tp(p, act) ? flat_occl_tp(p, r, ob, act, wc) : flat_occl_w(p, r, ob, act, w, wc);
-  if (walk & RT_RAYS_WALK_EXACT) {  // the proven closest walk: any winner shadows
-    Best b;
-    b.dist = __builtin_inff();
-    b.t_cut = __builtin_inff();
-    b.prim = 0xffffffffu;
-    b.obj = 0;
-    b.u = b.v = 0.0f;
-    b.t = 0.0f;
-    LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (act) {
-      oct_closest_rf<false>(p, r, b, s, lc);
-      if (b.dist != __builtin_inff()) lc.risk |= __float_as_uint(p.tri_prim[3 * (size_t)b.prim + 2].w) & RT_REC_ZERO_RISK;
-    }
-    absorb<false>(wc, lc, true);
-    return act && b.dist != __builtin_inff();
-  }
-  if (walk & RT_RAYS_WALK_PACKET) return staged_occl(p, r, ob, act, w, wc);
-  LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
-  const bool hit = act && oct_occl(p, r, ob, s, lc);
-  absorb<false>(wc, lc, true);
-  return hit;
+  return occl_oct<false>(p, r, ob, act, walk, s, w, wc);  // the exact route: any winner shadows
 }
 
 // Phase 1 of a chunk of 32 lights: the mask of the chunk's casting lights that
@@ -127,19 +107,9 @@ __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void dlight_kernel(KParams 
   WorkCount wc = {};
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : kStackArea];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : kStageOct];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   const uint32_t home = (uint32_t)blockIdx.x & 7u;
   uint32_t probe = 0;
   bool first = true;

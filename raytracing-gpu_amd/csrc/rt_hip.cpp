@@ -918,7 +918,7 @@ extern "C" int rt_hip_stats(rt_hip_ctx* c, rt_stats* out) {
   RT_CTX_LIVE(c);
   HIP_TRY(hipSetDevice(c->device));
   // an occlusion batch counted into its own block and touched nothing a
-  // frame's readers use (csrc/rt_occl.cpp)
+  // frame's readers use (csrc/rt_batch.cpp)
   if (c->last_occl) return occl_stats(c, out);
   unsigned long long hs[RT_STAT_SETS * RT_STAT_STRIDE], h[RT_NSTATS];
   uint32_t hc[RT_HIT_REGIONS * RT_HIT_STRIDE];

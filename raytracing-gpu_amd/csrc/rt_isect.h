@@ -149,6 +149,18 @@ struct Best {
   float t;  // the winner's MT t; its hit point is hit_point(r, t)
 };
 
+// No hit yet: what a closest-hit query starts from.
+__device__ __forceinline__ Best best_none() {
+  Best b;
+  b.dist = __builtin_inff();
+  b.t_cut = __builtin_inff();
+  b.prim = 0xffffffffu;
+  b.obj = 0;
+  b.u = b.v = 0.0f;
+  b.t = 0.0f;
+  return b;
+}
+
 __device__ __forceinline__ void consider_exact(const Ray& r, const float4& q0, const float4& q1,
                                                const float4& q2, Best& b);
 

@@ -321,20 +321,23 @@ extern "C" hipError_t rt_launch_rays_samples(const KParams* p, const RayArgs* a,
 // rt_hip_frame_rays: the 4 W H camera rays of p's frame (p->u, v, C, pos, W, H)
 // in pixel order (order 0) or quarter order (1), csrc/rt_ray_items.h
 extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* org, float* dir, hipStream_t stream);
-// An occlusion batch (csrc/rt_occl.h): its one kernel, one-wave workgroups
-// pulling items of 64 rays, and that kernel's persistent grid on `cus` CUs
-extern "C" hipError_t rt_launch_occl(const KParams* p, const OcclArgs* a, int accel, int grid, hipStream_t stream);
-extern "C" hipError_t rt_occl_grid(int accel, int cus, int* grid);
-// Ambient occlusion from records (csrc/rt_ao.h): the fused kernel (generate,
-// walk, count) on one-wave workgroups pulling items of whole samples, its
-// persistent grid (k <= 64 and k > 64 are two kernels), and the generator alone, one thread per ray
-extern "C" hipError_t rt_launch_ao(const KParams* p, const AoArgs* a, int accel, int grid, hipStream_t stream);
-extern "C" hipError_t rt_ao_grid(int accel, int wide, int cus, int* grid);  // wide: k > 64
+// The batches that count into the batch stats block (csrc/rt_batch.h): an
+// occlusion batch (csrc/rt_occl.h, args = OcclArgs), ambient occlusion from
+// records (csrc/rt_ao.h, AoArgs; k <= 64 and k > 64 are two kernels) and direct
+// light for records (csrc/rt_dlight.h, DlArgs).  Each kind is one kernel on
+// one-wave workgroups pulling work items; rt_batch_grid is that kernel's
+// persistent grid on `cus` CUs, rt_launch_batch its launch with `args`, the
+// kind's own block.
+#define RT_BATCH_OCCL 0
+#define RT_BATCH_AO 1
+#define RT_BATCH_AO_WIDE 2
+#define RT_BATCH_DLIGHT 3
+#define RT_NBATCH 4
+extern "C" hipError_t rt_launch_batch(const KParams* p, const void* args, int kind, int accel, int grid,
+                                      hipStream_t stream);
+extern "C" hipError_t rt_batch_grid(int kind, int accel, int cus, int* grid);
+// ambient occlusion's generator alone, one thread per ray
 extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream);
-// Direct light for records (csrc/rt_dlight.h): its one kernel, one-wave
-// workgroups pulling items of 64 records, and that kernel's persistent grid
-extern "C" hipError_t rt_launch_dlight(const KParams* p, const DlArgs* a, int accel, int grid, hipStream_t stream);
-extern "C" hipError_t rt_dlight_grid(int accel, int cus, int* grid);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

@@ -255,36 +255,41 @@ __device__ bool staged_occl(const KParams& p, const Ray& r, const OcclBound& ob,
   return hit;
 }
 
-// The batch's query; walk is wave-uniform (OcclArgs::walk).  Converged call,
-// act = the lane makes a query.
-template <int ACCEL>
-__device__ __forceinline__ bool occl_q(const KParams& p, const Ray& r, float tmax, bool act, uint32_t walk, Stack& s,
-                                       WaveCtx& w, WorkCount& wc) {
-  const OcclBound ob = occl_bound(r, tmax);
-  if (ACCEL == RT_ACCEL_FLAT_D) return use_tp(p, act) ? flat_occl_tp(p, r, ob, act, wc) : flat_occl_w(p, r, ob, act, w, wc);
+// The octree routes of a batch query with the bound `ob`, for occl_q and for
+// direct light's dlight_q (rt_dlight.h); walk is wave-uniform (OcclArgs::walk).
+// BOUNDED: the exact route's winner occludes only within ob.tmax (without it any
+// winner does).  Converged call, act = the lane makes a query.
+// (The FLAT route stays with the two callers: through this function the FLAT
+// kernels' scalar register numbering changed.)
+template <bool BOUNDED>
+__device__ __forceinline__ bool occl_oct(const KParams& p, const Ray& r, const OcclBound& ob, bool act, uint32_t walk,
+                                         Stack& s, WaveCtx& w, WorkCount& wc) {
   if (walk & RT_RAYS_WALK_EXACT) {
     // the proven closest walk, answering dist <= tmax; the winner's object
     // flag (its record, prim order) is the zero-normal risk
-    Best b;
-    b.dist = __builtin_inff();
-    b.t_cut = __builtin_inff();
-    b.prim = 0xffffffffu;
-    b.obj = 0;
-    b.u = b.v = 0.0f;
-    b.t = 0.0f;
+    Best b = best_none();
     LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
     if (act) {
       oct_closest_rf<false>(p, r, b, s, lc);
       if (b.dist != __builtin_inff()) lc.risk |= __float_as_uint(p.tri_prim[3 * (size_t)b.prim + 2].w) & RT_REC_ZERO_RISK;
     }
     absorb<false>(wc, lc, true);
-    return act && b.dist != __builtin_inff() && b.dist <= tmax;
+    return act && b.dist != __builtin_inff() && (!BOUNDED || b.dist <= ob.tmax);
   }
   if (walk & RT_RAYS_WALK_PACKET) return staged_occl(p, r, ob, act, w, wc);
   LaneCount lc = {0, 0, 0, 0, 0, 0, 0, 0};
   const bool hit = act && oct_occl(p, r, ob, s, lc);
   absorb<false>(wc, lc, true);
   return hit;
+}
+
+// The batch's query: within the ray's tmax.
+template <int ACCEL>
+__device__ __forceinline__ bool occl_q(const KParams& p, const Ray& r, float tmax, bool act, uint32_t walk, Stack& s,
+                                       WaveCtx& w, WorkCount& wc) {
+  const OcclBound ob = occl_bound(r, tmax);
+  if (ACCEL == RT_ACCEL_FLAT_D) return use_tp(p, act) ? flat_occl_tp(p, r, ob, act, wc) : flat_occl_w(p, r, ob, act, w, wc);
+  return occl_oct<true>(p, r, ob, act, walk, s, w, wc);
 }
 
 // Occlusion batch: a work item is 64 consecutive rays, lane = ray, on
@@ -298,19 +303,9 @@ __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void rays_occl_kernel(KPara
   WorkCount wc = {};
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : kStackArea];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : kStageOct];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   const uint32_t home = (uint32_t)blockIdx.x & 7u;
   uint32_t probe = 0;
   bool first = true;

@@ -49,12 +49,7 @@ __global__ __launch_bounds__(64) void probe_closest_kernel(KParams p, const floa
   const int lane = threadIdx.x & 63;
   const uint32_t i = blockIdx.x * 64u + (uint32_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + (size_t)blockIdx.x * 64 + (size_t)lane;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
+  lane_stack(p, s_stack, lane, stk);
   const bool act = i < n;
   f3 o{0.0f, 0.0f, 0.0f}, d{0.0f, 0.0f, 1.0f};
   if (act) {
@@ -62,13 +57,7 @@ __global__ __launch_bounds__(64) void probe_closest_kernel(KParams p, const floa
     d = f3{dir[3 * (size_t)i], dir[3 * (size_t)i + 1], dir[3 * (size_t)i + 2]};
   }
   const Ray r = make_ray(p, o, d, p.eps_rel);
-  Best b;
-  b.dist = __builtin_inff();
-  b.t_cut = __builtin_inff();
-  b.prim = 0xffffffffu;
-  b.obj = 0;
-  b.u = b.v = 0.0f;
-  b.t = 0.0f;
+  Best b = best_none();
   if (brute) {
     if (act)
       for (uint32_t k = 0; k < nprim; k++) {

@@ -3,7 +3,7 @@
 // refusals, its share of the context's hit-record buffers, its kernels
 // (csrc/rt_rays.h) and launches, in the steps of rt_hip_render (rt_hip.cpp).
 // The item count, the buffers' sizing and the ray orders are csrc/rt_ray_items.h.
-#include "rt_ctx.h"
+#include "rt_batch.h"  // the refusals every batch words alike
 
 static_assert(RT_RAYS_MAX == RT_RAY_BATCH_MAX, "rt_hip.h states what a record index addresses");
 
@@ -11,18 +11,12 @@ static_assert(RT_RAYS_MAX == RT_RAY_BATCH_MAX, "rt_hip.h states what a record in
 // (origins, dirs, rgb, samples: device pointers, or the host wrapper's)
 static int rays_refuse(const rt_hip_ctx* c, const float* origins, const float* dirs, size_t n, unsigned flags,
                        const float* rgb, const void* samples) {
-  if (!c) return rt_set_error(RT_EINVAL, "null context");
-  RT_CTX_LIVE(c);
+  if (int rc = batch_refuse_ctx(c)) return rc;
   if (!rgb && !samples) return rt_set_error(RT_EINVAL, "a ray batch needs a colour or a sample output");
   if (n && (!origins || !dirs)) return rt_set_error(RT_EINVAL, "null rays");
   if (n > RT_RAYS_MAX)
     return rt_set_error(RT_EINVAL, "%zu rays: a hit record's index addresses %llu", n, (unsigned long long)RT_RAYS_MAX);
-  if (flags & ~RT_RAYS_PACKET) return rt_set_error(RT_EINVAL, "unknown ray batch flags %#x", flags);
-  // the batch's trace exists for the default kernels only, like the G-buffer's
-  if (c->policy != RT_POLICY_DEFAULT)
-    return rt_set_error(RT_EINVAL, "a ray batch needs the default traversal policy (have %d)", c->policy);
-  if (c->count_work) return rt_set_error(RT_EINVAL, "a ray batch cannot run as the work-counting pass");
-  return RT_OK;
+  return batch_refuse_mode(c, flags, "a ", "ray batch");
 }
 
 extern "C" int rt_hip_trace_rays(rt_hip_ctx* c, const float* d_origins, const float* d_dirs, size_t n,
@@ -102,10 +96,7 @@ extern "C" int rt_hip_trace_rays_host(rt_hip_ctx* c, const float* h_origins, con
                                       unsigned flags, float* h_rgb, rt_gsample* h_samples, rt_stats* st) {
   int rc = rays_refuse(c, h_origins, h_dirs, n, flags, h_rgb, h_samples);
   if (rc) return rc;
-  if (n == 0) {  // nothing launched, nothing written
-    if (st) std::memset(st, 0, sizeof *st);
-    return RT_OK;
-  }
+  if (n == 0) return batch_host_none(st);
   HIP_TRY(hipSetDevice(c->device));
   DevBuf<float> d_o, d_d, d_rgb;
   DevBuf<uint32_t> d_smp;

@@ -24,25 +24,17 @@ static_assert(RT_REC_REGIONS == RT_HIT_REGIONS, "rt_ray_items.h states the recor
 // Every item writes its lanes' deepest records (p.last[64 item + lane]) and,
 // under RT_POLICY_RAYS_GB, their capture records.  A ray past the batch's end
 // or one that is not traced (rt_ray_traced) makes no query.
+// (The item claim stays inline here and in the other kernels that pull items
+// this way: through a shared function their scalar register allocation changed.)
 template <int ACCEL, int POL>
 __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void rays_trace_kernel(KParams p, RayArgs a) {
   const int lane = threadIdx.x & 63;
   WorkCount wc = {};
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : kStackArea];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : kStageOct];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   const uint32_t home = (uint32_t)blockIdx.x & 7u;
   uint32_t probe = 0;
   bool first = true;

@@ -167,13 +167,7 @@ __device__ __forceinline__ uint32_t trace_path(const KParams& p, bool valid, f3 
     wc.closest += (uint32_t)__popcll(am);  // wave-uniform counters (SGPRs)
     if (kCapture && alive) cap.queries++;  // the lane's own share of wc.closest
     Ray r = make_ray(p, o, d, depth == 0 && !kRays ? p.eps_rel_cam : p.eps_rel);
-    Best b;
-    b.dist = __builtin_inff();
-    b.t_cut = __builtin_inff();
-    b.prim = 0xffffffffu;
-    b.obj = 0;
-    b.u = b.v = 0.0f;
-    b.t = 0.0f;
+    Best b = best_none();
     uint64_t c0 = COUNT ? __builtin_readcyclecounter() : 0ull;
     if constexpr (kRays)
       rays_closest<ACCEL>(p, r, alive, depth, walk, b, s, w, wc);
@@ -240,24 +234,11 @@ template <int ACCEL, bool COUNT, int POL>
 __global__ __launch_bounds__(64, RT_TRACE_MIN_WAVES) void trace_kernel(KParams p) {
   const int lane = threadIdx.x & 63;
   WorkCount wc = {};
-  // The per-lane stacks and the staged wave stack share one LDS area: a
-  // wave runs one walk at a time and every walk starts and ends with an
-  // empty stack (wave_sync() at both ends orders the accesses).
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : kStackArea];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : kStageOct];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   // Work item = (tile t, quarter q): a tile's 256 camera rays run on four
   // waves, so a tile of long mirror paths (C2: the worst tile cost 7.7x a
   // balanced schedule's whole frame, tools/tile_cost.py) is not one wave's
@@ -424,19 +405,9 @@ __global__ __launch_bounds__(64, ACCEL == RT_ACCEL_FLAT_D ? RT_FLAT_SHADE_MIN_WA
   constexpr bool kStaged = POL == RT_POLICY_STAGED || POL == RT_POLICY_DIR_STAGED;
   __shared__ float4 s_stack[ACCEL == RT_ACCEL_FLAT_D ? 1 : (kStaged ? kStackArea : kLaneStackArea)];
   __shared__ float4 s_stage[ACCEL == RT_ACCEL_FLAT_D ? kStageFlat : (kStaged ? kStageOct : 1)];
-  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
   Stack stk;
-  stk.idx = (uint32_t*)s_stack;
-  stk.tt = (float*)s_stack + kLdsStack * 64;
-  stk.spill = p.spill + gl;
-  stk.stride = gridDim.x * 64u;
-  stk.lane = lane;
-  stk.sp = 0;
   WaveCtx w;
-  w.stk2 = s_stack;
-  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
-  w.stage = s_stage;
-  w.lane = lane;
+  wave_state(p, s_stack, s_stage, lane, stk, w);
   const uint32_t home = (uint32_t)blockIdx.x & 7u;
   uint32_t probe = 0;
   bool first_chunk = true;
@@ -1012,53 +983,24 @@ extern "C" hipError_t rt_launch_frame_rays(const KParams* p, int order, float* o
   return hipGetLastError();
 }
 
-// An occlusion batch's launch (rt_kernels.h, csrc/rt_occl.h).  Last, for the
-// same reason again: every earlier kernel keeps its place.
+// The batches that count into the batch stats block (rt_kernels.h RT_BATCH_*;
+// csrc/rt_occl.h, rt_ao.h, rt_dlight.h): one kernel per (kind, accel).  Last, for
+// the same reason again.  The kernels are emitted in the order this file first
+// names them, so the kinds' lookups stand in the order the kinds were added,
+// ambient occlusion's generator between its fused kernel and direct light:
+// every kernel keeps its place.
 static const void* occl_kernel_of(int accel) {
   return accel == RT_ACCEL_FLAT_D ? (const void*)rt::rays_occl_kernel<RT_ACCEL_FLAT_D>
                                   : (const void*)rt::rays_occl_kernel<RT_ACCEL_OCTREE_D>;
 }
 
-extern "C" hipError_t rt_occl_grid(int accel, int cus, int* grid) {
-  int per_cu = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, occl_kernel_of(accel), 64, 0);
-  if (e != hipSuccess) return e;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 32) per_cu = 32;
-  *grid = per_cu * cus;
-  return hipSuccess;
-}
-
-extern "C" hipError_t rt_launch_occl(const KParams* p, const OcclArgs* a, int accel, int grid, hipStream_t stream) {
-  if (grid <= 0) return hipErrorInvalidValue;
-  void* args[] = {(void*)p, (void*)a};
-  return hipLaunchKernel(occl_kernel_of(accel), dim3(grid), dim3(64), args, 0, stream);
-}
-
-// Ambient occlusion from records (rt_kernels.h, csrc/rt_ao.h).  Last, for the
-// same reason once more: every earlier kernel keeps its place.
 static const void* ao_kernel_of(int accel, bool wide) {  // wide: k > 64
   if (accel == RT_ACCEL_FLAT_D)
     return wide ? (const void*)rt::ao_kernel<RT_ACCEL_FLAT_D, true> : (const void*)rt::ao_kernel<RT_ACCEL_FLAT_D, false>;
   return wide ? (const void*)rt::ao_kernel<RT_ACCEL_OCTREE_D, true> : (const void*)rt::ao_kernel<RT_ACCEL_OCTREE_D, false>;
 }
 
-extern "C" hipError_t rt_ao_grid(int accel, int wide, int cus, int* grid) {
-  int per_cu = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ao_kernel_of(accel, wide != 0), 64, 0);
-  if (e != hipSuccess) return e;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 32) per_cu = 32;
-  *grid = per_cu * cus;
-  return hipSuccess;
-}
-
-extern "C" hipError_t rt_launch_ao(const KParams* p, const AoArgs* a, int accel, int grid, hipStream_t stream) {
-  if (grid <= 0) return hipErrorInvalidValue;
-  void* args[] = {(void*)p, (void*)a};
-  return hipLaunchKernel(ao_kernel_of(accel, a->k > 64u), dim3(grid), dim3(64), args, 0, stream);
-}
-
+// Ambient occlusion's generator alone (csrc/rt_ao.h), one thread per ray.
 extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream) {
   const unsigned long long blocks = (a->n * a->k + 255) / 256;
   if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
@@ -1066,16 +1008,21 @@ extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// Direct light for records (rt_kernels.h, csrc/rt_dlight.h).  Last, for the
-// same reason yet again: every earlier kernel keeps its place.
 static const void* dlight_kernel_of(int accel) {
   return accel == RT_ACCEL_FLAT_D ? (const void*)rt::dlight_kernel<RT_ACCEL_FLAT_D>
                                   : (const void*)rt::dlight_kernel<RT_ACCEL_OCTREE_D>;
 }
 
-extern "C" hipError_t rt_dlight_grid(int accel, int cus, int* grid) {
+static const void* batch_kernel_of(int kind, int accel) {
+  if (kind == RT_BATCH_OCCL) return occl_kernel_of(accel);
+  if (kind == RT_BATCH_DLIGHT) return dlight_kernel_of(accel);
+  return ao_kernel_of(accel, kind == RT_BATCH_AO_WIDE);
+}
+
+// Its persistent grid, as rt_render_grid's.
+extern "C" hipError_t rt_batch_grid(int kind, int accel, int cus, int* grid) {
   int per_cu = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dlight_kernel_of(accel), 64, 0);
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, batch_kernel_of(kind, accel), 64, 0);
   if (e != hipSuccess) return e;
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 32) per_cu = 32;
@@ -1083,8 +1030,10 @@ extern "C" hipError_t rt_dlight_grid(int accel, int cus, int* grid) {
   return hipSuccess;
 }
 
-extern "C" hipError_t rt_launch_dlight(const KParams* p, const DlArgs* a, int accel, int grid, hipStream_t stream) {
+// args: the kind's own block (OcclArgs, AoArgs, DlArgs)
+extern "C" hipError_t rt_launch_batch(const KParams* p, const void* args, int kind, int accel, int grid,
+                                      hipStream_t stream) {
   if (grid <= 0) return hipErrorInvalidValue;
-  void* args[] = {(void*)p, (void*)a};
-  return hipLaunchKernel(dlight_kernel_of(accel), dim3(grid), dim3(64), args, 0, stream);
+  void* kargs[] = {(void*)p, (void*)args};
+  return hipLaunchKernel(batch_kernel_of(kind, accel), dim3(grid), dim3(64), kargs, 0, stream);
 }

@@ -32,6 +32,19 @@ struct Stack {
   int sp;
 };
 
+// The empty stack of `lane` in a one-wave workgroup: its LDS entries in the
+// kernel's stack area, its spill entries in p.spill.  (gl first, as the kernels
+// had it: formed inside the pointer expression, eight kernels' registers moved.)
+__device__ __forceinline__ void lane_stack(const KParams& p, float4* s_stack, int lane, Stack& stk) {
+  const size_t gl = (size_t)blockIdx.x * 64 + (size_t)lane;
+  stk.idx = (uint32_t*)s_stack;
+  stk.tt = (float*)s_stack + kLdsStack * 64;
+  stk.spill = p.spill + gl;
+  stk.stride = gridDim.x * 64u;
+  stk.lane = lane;
+  stk.sp = 0;
+}
+
 // Counters of one lane's own walk (divergent code); folded into the wave's
 // WorkCount after the walk (absorb).
 struct LaneCount {

@@ -69,6 +69,19 @@ struct WaveCtx {
   int lane;
 };
 
+// A wave's walk state from its kernel's two LDS arrays (declared there: their
+// sizes differ per kernel).  The per-lane stacks and the staged wave stack
+// share one LDS area: a wave runs one walk at a time and every walk starts and
+// ends with an empty stack (wave_sync() at both ends orders the accesses).
+__device__ __forceinline__ void wave_state(const KParams& p, float4* s_stack, float4* s_stage, int lane, Stack& stk,
+                                           WaveCtx& w) {
+  lane_stack(p, s_stack, lane, stk);
+  w.stk2 = s_stack;
+  w.stkm = (uint64_t*)(s_stack + 2 * kStack2);
+  w.stage = s_stage;
+  w.lane = lane;
+}
+
 // A fetch in flight: the wave's lanes hold float4 k, k+64, k+128 of src[0, n)
 // in registers (issued early so its latency overlaps other work), then commit
 // it to the LDS stage; n <= NMAX <= kStageFlat.  NMAX is the caller's bound on
@@ -223,13 +236,7 @@ __device__ void flat_closest_tp(const KParams& p, const Ray& r, bool act, Best& 
     const int l = __ffsll((unsigned long long)am) - 1;
     am &= am - 1;
     const Ray q = ray_of_lane(r, l);
-    Best mb;
-    mb.dist = __builtin_inff();
-    mb.t_cut = __builtin_inff();
-    mb.prim = 0xffffffffu;
-    mb.obj = 0;
-    mb.u = mb.v = 0.0f;
-    mb.t = 0.0f;
+    Best mb = best_none();
     for (uint32_t base = 0; base < n; base += 64) {
       const uint32_t i = base + (uint32_t)lane;
       if (i < n) {

@@ -553,6 +553,67 @@ def test_direct_light_between_streamed_frames(gpu, scene_dir, shared):
         assert a.tobytes() == sh["flat"][0].tobytes() and b.tobytes() == sh["flat"][1].tobytes()
 
 
+@pytest.mark.parametrize("accel", ["flat", "octree"])
+def test_batch_kinds_share_one_path(gpu, shared, accel):
+    """An occlusion batch, ambient occlusion with k = 3 and with k = 65 (the
+    wide kernel) and a direct-light call share the context's batch stats
+    block, grid table and last-batch bookkeeping.  Each runs twice on one
+    context's own stream, in two orders, stats() read after every call: every
+    output word and every stats dictionary is what the same call gives as the
+    first and only call on a fresh context of the same kind.  Shapes: 130
+    rays / records (three items, the last partial), 45 records at k = 3 (21
+    samples an item: three items, the last partial), 3 records at k = 65."""
+    sh = shared("spheres")
+    s = sh["scene"]
+    hit = sh["hits"][sh["hits"]["prim"] >= 0]
+    assert len(hit) >= 130
+    every = len(hit) // 130
+    o, d = gpu.camera_rays(s.frame(), "pixel")
+    o, d = o[::17][:130], d[::17][:130]
+    tmax = np.where(np.arange(130) % 3 == 0, F32(np.inf), F32(2.0) * F32(_radius(s))).astype(F32)
+    table = gpu.ao_table(16, 7)
+    rec_dl, rec_ao, rec_wide = hit[::every][:130], hit[1::2 * every][:45], hit[2::40][:3]
+    assert len(o) == len(rec_dl) == 130 and len(rec_ao) == 45 and len(rec_wide) == 3
+    dev = Dev(gpu)
+    d_o, d_d, d_t, d_tab = dev.upload(o), dev.upload(d), dev.upload(tmax), dev.upload(table)
+    d_dl, d_ao, d_wide = dev.upload(rec_dl), dev.upload(rec_ao), dev.upload(rec_wide)
+
+    def occl(ctx):
+        d_out = dev.upload(np.full(130, FILL, np.uint8))
+        ctx.occluded_device(d_o, d_d, d_t, 130, d_out)
+        return ctx.stats(), [dev.host(d_out, 130, np.uint8)]
+
+    def ao(ctx, d_rec, n, k):
+        d_out = dev.upload(np.full(n, FILL32, np.uint32))
+        ctx.ambient_occlusion_device(d_rec, n, k, d_tab, len(table), 5, d_out, tmax=_radius(s))
+        return ctx.stats(), [dev.host(d_out, n, np.uint32)]
+
+    def dl(ctx):
+        d_rgb, d_lit = dev.upload(np.full(3 * 130, FILL32, np.uint32)), dev.upload(np.full(130, FILL32, np.uint32))
+        ctx.direct_light_device(d_dl, 130, d_rgb, d_lit)
+        return ctx.stats(), [dev.host(d_rgb, 3 * 130, np.uint32), dev.host(d_lit, 130, np.uint32)]
+
+    calls = {"occluded": occl, "ao k=3": lambda c: ao(c, d_ao, 45, 3), "ao k=65": lambda c: ao(c, d_wide, 3, 65),
+             "direct light": dl}
+    alone = {}
+    for what, call in calls.items():
+        ctx = gpu.Context(s, accel)
+        alone[what] = call(ctx)
+        ctx.close()
+    assert alone["occluded"][0]["shadow"] > 0 and alone["ao k=3"][0]["shadow"] > 0 and alone["ao k=65"][0]["shadow"] > 0
+    assert alone["direct light"][0]["camera"] > 0 and alone["occluded"][1][0].max() == 1
+    assert len({json.dumps(st, sort_keys=True) for st, _ in alone.values()}) >= 3, "a stale stats block would show"
+    ctx = gpu.Context(s, accel)
+    order = list(calls)
+    for what in order + order[::-1]:
+        st, outs = calls[what](ctx)
+        assert st == alone[what][0], (accel, what, st, alone[what][0])
+        for got, want in zip(outs, alone[what][1]):
+            assert got.tobytes() == want.tobytes(), (accel, what)
+    ctx.close()
+    dev.close()
+
+
 # ---- 9: refusals ----------------------------------------------------------------------------------------------------
 def test_refusals_change_nothing(gpu, shared):
     sh = shared("spheres")
