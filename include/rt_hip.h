@@ -613,6 +613,63 @@ int rt_hip_ao_rays_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n, 
                         unsigned k, const float *h_table, unsigned m, unsigned seed, float *h_origins,
                         float *h_dirs, unsigned char *h_shot /* may be NULL */);
 
+/* Traced light gathered over a record's hemisphere (new): what a lightmap
+ * bake, a probe bake or a one-bounce final gather needs -- for each of n
+ * rt_gsample records in device memory, k rays over its hemisphere, the
+ * reference's trace(ray, 1.0) on each, and the colours added up.  The records,
+ * n, base, k, d_table, m and seed are rt_hip_ambient_occlusion's, and so are
+ * the rays; they are made in the trace kernel and exist in no array.  There is
+ * no tmax.
+ *
+ * The contract is a composition of calls above.  Let (o_j, d_j), j = i k + r,
+ * be the rays rt_hip_ao_rays writes for the same records, k, table, m, seed
+ * and base, and c_j the colour rt_hip_trace_rays writes for ray j on this
+ * context in its current settings (an untraced ray has colour 0: that covers a
+ * record that does not shoot, whose directions are all zero).  Then
+ *     d_rgb[3i .. 3i+2] = acc_k,  acc_0 = (+0, +0, +0),
+ *     acc_{r+1} = color_add(acc_r, c_{i k + r})        (cpu/colors.c: a float
+ *                 add per channel, then the clamp `if (x > 255) x = 255`)
+ * in ray order, in float, one add per channel per ray.  That order is the
+ * rule: no tree or wave reduction replaces it.  The sum is not divided by k
+ * and carries no cosine or weight: the caller's table is the distribution.
+ * rtgpu.gather_sum is the rule's numpy float32 twin.  Every word of [0, 3 n)
+ * is written exactly once, with plain stores, nothing past it; the output
+ * needs no clearing.  k ranges over 1 .. RT_AO_KMAX.
+ *
+ * The queries are a reflection ray's, as a ray batch's: tested against brute
+ * force by default, proven under rt_hip_set_exact_reflections, brute force on
+ * a FLAT context; no candidate list.  Table directions are near unit length; a
+ * longer one (|d| > 1.0625) counts in closest_unproven under the proven walk,
+ * as for a batch.  RT_RAYS_PACKET means what it means for a ray batch: each
+ * work item's rays (whole records side by side, 64 / k of them; one record's
+ * rounds of 64 for k > 64) walk their first query as one packet -- the same
+ * bits, only faster for coherent groups; ignored on FLAT and under exact
+ * reflections.
+ *
+ * To the context a gather is a ray batch.  It uses and overwrites the
+ * hit-record buffers (first sized for two records per path): rt_hip_relight
+ * and rt_hip_gbuffer return RT_EINVAL after it until the next rt_hip_render.
+ * rt_hip_stats after it reads as after rt_hip_trace_rays on those rays: camera
+ * = rays traced, pixels = 0, cand_* = 0, every other counter as for a render;
+ * on RT_EHITBUF the buffers grow and the call must be made again.
+ * rt_hip_frame_check accounts it like a batch.  It touches no candidate list:
+ * a gather between two frames of a streaming caller leaves both as they are.
+ * Asynchronous on `stream`, with rt_hip_render's threading rules.
+ *
+ * RT_EINVAL with nothing changed: a NULL context; NULL samples, table or d_rgb
+ * with n > 0; samples not 8-byte aligned; k == 0 or k > RT_AO_KMAX; m == 0;
+ * n k > RT_RAYS_MAX; flags other than RT_RAYS_PACKET; a non-default traversal
+ * policy; rt_hip_set_count_work; a context left broken by a failed geometry
+ * update.  n == 0 returns RT_OK and writes nothing. */
+int rt_hip_gather(rt_hip_ctx *ctx, const void *d_samples, size_t n, unsigned long long base, unsigned k,
+                  const float *d_table, unsigned m, unsigned seed, unsigned flags, float *d_rgb,
+                  void *stream);
+/* Upload, rt_hip_gather on the context's stream, download, rt_hip_stats;
+ * synchronous.  Gathers again once after RT_EHITBUF, as rt_hip_trace_rays_host. */
+int rt_hip_gather_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n, unsigned long long base,
+                       unsigned k, const float *h_table, unsigned m, unsigned seed, unsigned flags,
+                       float *h_rgb, rt_stats *stats);
+
 /* Direct light for caller's surface records (new): for each of n rt_gsample
  * records in device memory (8-byte aligned; a rank's tile buffer straight from
  * rt_hip_gbuffer, the assembled samples, a ray batch's records, or points of

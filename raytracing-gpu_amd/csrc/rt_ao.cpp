@@ -9,9 +9,10 @@
 
 static_assert(RT_AO_KMAX == RT_AO_KMAX_D, "include/rt_hip.h and csrc/rt_ao_items.h disagree on k's limit");
 
-// What the three entry points refuse alike, by the sizes alone; nothing of the
-// context has changed when a refusal returns.
-static int ao_refuse(const rt_hip_ctx* c, size_t n, unsigned k, unsigned m) {
+// What the entry points (and a gather's, csrc/rt_gather.cpp: declared in
+// rt_batch.h) refuse alike, by the sizes alone; nothing of the context has
+// changed when a refusal returns.
+int ao_refuse(const rt_hip_ctx* c, size_t n, unsigned k, unsigned m) {
   if (int rc = batch_refuse_ctx(c)) return rc;
   if (k == 0 || k > RT_AO_KMAX) return rt_set_error(RT_EINVAL, "%u rays per sample: 1 to %u", k, (unsigned)RT_AO_KMAX);
   if (m == 0) return rt_set_error(RT_EINVAL, "an empty direction table");
@@ -23,7 +24,7 @@ static int ao_refuse(const rt_hip_ctx* c, size_t n, unsigned k, unsigned m) {
   return RT_OK;
 }
 // ... and the records and table in device memory
-static int ao_refuse_ptrs(const void* d_samples, size_t n, const float* d_table) {
+int ao_refuse_ptrs(const void* d_samples, size_t n, const float* d_table) {
   if (n && (!d_samples || !d_table)) return rt_set_error(RT_EINVAL, "null samples or table");
   if ((uintptr_t)d_samples & 7u) return rt_set_error(RT_EINVAL, "samples must be 8-byte aligned");
   return RT_OK;

@@ -17,6 +17,12 @@ int batch_refuse_ctx(const rt_hip_ctx* c);  // null or broken
 int batch_refuse_size(size_t n, const char* things);
 int batch_refuse_mode(const rt_hip_ctx* c, unsigned flags, const char* a, const char* noun);  // flags, policy, counting pass
 
+// Batches over rt_gsample records with k rays each by ambient occlusion's rule
+// (rt_ao.cpp, rt_gather.cpp): the sizes (k, m, n k, the item count), and the
+// records and table in device memory.
+int ao_refuse(const rt_hip_ctx* c, size_t n, unsigned k, unsigned m);                // rt_ao.cpp
+int ao_refuse_ptrs(const void* d_samples, size_t n, const float* d_table);          // rt_ao.cpp
+
 // A launch worked out by batch_begin: the caller copies `walk` into its
 // argument block, checks the pointers only its kernel follows, and runs it.
 struct BatchLaunch {

@@ -184,6 +184,7 @@ struct rt_hip_ctx {
   int batch_grid[RT_NBATCH][2] = {};  // [RT_BATCH_*][RT_ACCEL_*_D]: the kernel's persistent grid (0: not asked yet)
   int last_occl = 0;
   hipStream_t occl_stream = nullptr;
+  int gather_grid[2][2] = {};  // [RT_ACCEL_*_D][k > 64]: a gather's trace kernel's persistent grid (0: not asked yet)
   KParams last_p{};                 // the last render's parameters (rt_hip_verify_shadows); its pointers are views into the buffers here
   // exact shadow rays (csrc/rt_shadow.hip), built for the slack sh_ulps
   DevBuf<float2> d_prim_mu;

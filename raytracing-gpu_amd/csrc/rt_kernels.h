@@ -274,6 +274,15 @@ struct DlArgs {
   uint32_t* lit;         // one word per record, or NULL
 };
 
+// What a gather's kernels take beside the KParams (csrc/rt_gather.h): ambient
+// occlusion's block for the records and the ray rule (out, tmax, org, dir and
+// shot unused; nitems = rt_gather_item_count, walk as RayArgs::walk without
+// the cast) and the sums out.
+struct GatherArgs {
+  AoArgs ao;
+  float* rgb;  // 3 floats per record
+};
+
 // The three launches of one render (policy = RT_POLICY_*, octree only):
 // trace (closest hits -> hit records), shade (shadow queries + Phong per
 // record -> terms), fold (terms -> the rank's tile buffer)
@@ -338,6 +347,16 @@ extern "C" hipError_t rt_launch_batch(const KParams* p, const void* args, int ki
 extern "C" hipError_t rt_batch_grid(int kind, int accel, int cus, int* grid);
 // ambient occlusion's generator alone, one thread per ray
 extern "C" hipError_t rt_launch_ao_rays(const AoArgs* a, hipStream_t stream);
+// A gather (csrc/rt_gather.h): its trace (the ray batches' policy
+// RT_POLICY_RAYS, one-wave workgroups pulling items of whole records; k <= 64
+// and k > 64 are two kernels), that kernel's persistent grid on `cus` CUs, and
+// the fold of every record's k paths into a->rgb with the frame check's
+// bookkeeping.  The shade pass between them is rt_launch_shade and
+// rt_launch_shade_fixup, as in a ray batch
+extern "C" hipError_t rt_launch_gather_trace(const KParams* p, const GatherArgs* a, int accel, int grid,
+                                             hipStream_t stream);
+extern "C" hipError_t rt_gather_grid(int accel, int wide, int cus, int* grid);
+extern "C" hipError_t rt_launch_gather_fold(const KParams* p, const GatherArgs* a, hipStream_t stream);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

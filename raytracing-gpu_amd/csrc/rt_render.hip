@@ -744,6 +744,7 @@ __global__ __launch_bounds__(256) void gbuffer_kernel(KParams p, uint32_t* __res
 #include "rt_rays.h"  // the ray batches' kernels: after those
 #include "rt_occl.h"  // the occlusion batches' kernel: after those
 #include "rt_ao.h"  // ambient occlusion from records: after those
+#include "rt_gather.h"  // traced light gathered from records (ao_ray): after it
 #include "rt_dlight.h"  // direct light for records: last
 
 // ---------------------------------------------------------------- launchers
@@ -1036,4 +1037,41 @@ extern "C" hipError_t rt_launch_batch(const KParams* p, const void* args, int ki
   if (grid <= 0) return hipErrorInvalidValue;
   void* kargs[] = {(void*)p, (void*)args};
   return hipLaunchKernel(batch_kernel_of(kind, accel), dim3(grid), dim3(64), kargs, 0, stream);
+}
+
+// A gather's launches (rt_kernels.h, csrc/rt_gather.h): the ray batches' policy,
+// k <= 64 and k > 64 two kernels.  Last, for the same reason once more: named
+// here first, its kernels are emitted after every kernel that existed.
+static const void* gather_kernel_of(int accel, bool wide) {  // wide: k > 64
+  using namespace rt;
+  if (accel == RT_ACCEL_FLAT_D)
+    return wide ? (const void*)gather_trace_kernel<RT_ACCEL_FLAT_D, RT_POLICY_RAYS, true>
+                : (const void*)gather_trace_kernel<RT_ACCEL_FLAT_D, RT_POLICY_RAYS, false>;
+  return wide ? (const void*)gather_trace_kernel<RT_ACCEL_OCTREE_D, RT_POLICY_RAYS, true>
+              : (const void*)gather_trace_kernel<RT_ACCEL_OCTREE_D, RT_POLICY_RAYS, false>;
+}
+
+// Its persistent grid, as rt_render_grid's.
+extern "C" hipError_t rt_gather_grid(int accel, int wide, int cus, int* grid) {
+  int per_cu = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gather_kernel_of(accel, wide != 0), 64, 0);
+  if (e != hipSuccess) return e;
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 32) per_cu = 32;
+  *grid = per_cu * cus;
+  return hipSuccess;
+}
+
+extern "C" hipError_t rt_launch_gather_trace(const KParams* p, const GatherArgs* a, int accel, int grid,
+                                             hipStream_t stream) {
+  if (grid <= 0) return hipErrorInvalidValue;
+  void* args[] = {(void*)p, (void*)a};
+  return hipLaunchKernel(gather_kernel_of(accel, a->ao.k > 64u), dim3(grid), dim3(64), args, 0, stream);
+}
+
+extern "C" hipError_t rt_launch_gather_fold(const KParams* p, const GatherArgs* a, hipStream_t stream) {
+  const unsigned long long blocks = (a->ao.n + 255) / 256;
+  if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((rt::gather_fold_kernel<0>), dim3((unsigned)blocks), dim3(256), 0, stream, *p, *a);
+  return hipGetLastError();
 }

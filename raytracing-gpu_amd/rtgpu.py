@@ -241,6 +241,10 @@ _PROTOS = [
                                  C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rt_hip_ao_rays_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p,
                                       C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rt_hip_gather", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p, C.c_uint,
+                                C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
+    ("rt_hip_gather_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p,
+                                     C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.POINTER(Stats)]),
     ("rt_hip_direct_light", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     ("rt_hip_direct_light_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
@@ -843,6 +847,26 @@ def ao_open_share(counts, samples, k):
     return 1.0 - c / float(k)
 
 
+def gather_sum(colours, k):
+    """The numpy float32 twin of a gather's accumulation (include/rt_hip.h
+    rt_hip_gather): the colours of n k rays, (n k, 3) in ray order i k + r ->
+    (n, 3) float32, acc = color_add(acc, colour) from (+0, +0, +0) over r = 0 ..
+    k - 1: one float32 add per channel per ray, then the reference's clamp `if
+    (x > 255) x = 255` (cpu/colors.c), sequentially in ray order -- no pairwise or
+    tree sum, no division by k, no weight."""
+    f = np.float32
+    c = np.ascontiguousarray(colours, dtype=f).reshape(-1, 3)
+    k = int(k)
+    assert k >= 1 and len(c) % k == 0
+    c = c.reshape(-1, k, 3)
+    acc = np.zeros((len(c), 3), f)
+    with np.errstate(all="ignore"):
+        for r in range(k):
+            acc = (acc + c[:, r, :]).astype(f)
+            acc = np.where(acc > f(255), f(255), acc)
+    return acc
+
+
 # ---- direct light for caller's records (include/rt_hip.h rt_hip_direct_light) ----
 def records_from_points(P, N, obj, prim=0):
     """GSAMPLE records for Context.direct_light from caller points: (n, 3)
@@ -1383,6 +1407,34 @@ class Context:
             RT_RAYS_PACKET if packet else 0, out.ctypes.data_as(C.c_void_p), C.byref(st))),
             "rt_hip_ambient_occlusion_host")
         return out, st.as_dict()
+
+    def gather_device(self, d_samples, n, k, d_table, m, seed, d_rgb, packet=False, base=0, stream=None):
+        """rt_hip_gather on device pointers (asynchronous): d_samples = n
+        GSAMPLE records (a tile buffer, assembled samples, a ray batch's
+        records, caller points), d_table = m rows of 3 floats, d_rgb receives
+        3 n floats: per record the sum of its k hemisphere rays' traced colours."""
+        _check(lib().rt_hip_gather(
+            self.h, C.c_void_p(d_samples) if d_samples else None, int(n), int(base), int(k),
+            C.c_void_p(d_table) if d_table else None, int(m), int(seed) & 0xffffffff,
+            RT_RAYS_PACKET if packet else 0, C.c_void_p(d_rgb) if d_rgb else None,
+            C.c_void_p(stream) if stream else None), "rt_hip_gather")
+
+    def gather(self, samples, k, table, seed, packet=False, base=0):
+        """The light each GSAMPLE record's k hemisphere rays bring back: the
+        rays are ao_rays_host's, made on the device, each traced as
+        trace_rays traces it, their colours summed per record by gather_sum's
+        rule (rt_hip_gather_host) -> (rgb (n, 3) float32: raw sums, not divided
+        by k, stats: those of the ray batch of the same rays)."""
+        smp = np.ascontiguousarray(samples, dtype=GSAMPLE).reshape(-1)
+        tab = np.ascontiguousarray(table, dtype=np.float32).reshape(-1, 3)
+        rgb = np.zeros((len(smp), 3), np.float32)
+        st = Stats()
+        self.last_rc = 0  # the call's return code (RT_EINEXACT passes _check_render after a parity-breaking knob)
+        self._check_render(self._keep_rc(lib().rt_hip_gather_host(
+            self.h, smp.ctypes.data_as(C.c_void_p), len(smp), int(base), int(k), tab.ctypes.data_as(C.c_void_p),
+            len(tab), int(seed) & 0xffffffff, RT_RAYS_PACKET if packet else 0, rgb.ctypes.data_as(C.c_void_p),
+            C.byref(st))), "rt_hip_gather_host")
+        return rgb, st.as_dict()
 
     def direct_light_device(self, d_samples, n, d_rgb, d_lit=0, packet=False, stream=None):
         """rt_hip_direct_light on device pointers (asynchronous): d_samples = n
