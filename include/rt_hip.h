@@ -726,6 +726,75 @@ int rt_hip_direct_light(rt_hip_ctx *ctx, const void *d_samples, size_t n, unsign
 int rt_hip_direct_light_host(rt_hip_ctx *ctx, const rt_gsample *h_samples, size_t n, unsigned flags,
                              float *h_rgb, unsigned *h_lit /* may be NULL */, rt_stats *stats);
 
+/* A ray batch's paths written out (new): every bounce as a surface record.
+ * The tracer keeps a hit record per bounce of every ray (P, N, coef, obj, the
+ * link to the bounce before it and, after the shade pass, its term
+ * color_mul(apply_light(...), coef)); the fold sums each ray's chain
+ * deepest-first.  This call hands the chains to the caller: a CSR offset per
+ * ray and, per path vertex, an rt_gsample that rt_hip_ambient_occlusion,
+ * rt_hip_direct_light, rt_hip_gather and rt_hip_ao_rays take as it is, the
+ * vertex's coef and its term.  What a mirror shows can then be given ambient
+ * occlusion or gathered light (a frame with indirect light is the sum over
+ * every vertex k of coef_k (direct_k + gathered_k)), and bounces can be shaded
+ * by the caller without tracing them again ray by ray.
+ *
+ * Which batch: the paths are those of the context's last rt_hip_trace_rays
+ * that traced (n > 0) with d_rgb != NULL, with or without d_samples or
+ * RT_RAYS_PACKET; n must be that batch's n.
+ *
+ * What a path is: the chain the batch's fold walked for ray i -- from the
+ * ray's deepest record, while the index names a record the buffers hold, along
+ * the links -- written out in reverse: vertex 0 is the ray's first hit, the
+ * last vertex the deepest.  len_i is the chain's length; a miss, an untraced
+ * ray (rt_hip_trace_rays) and a first-hit winner with a zero normal have
+ * len_i = 0.  The walk is bounded by the tracer's bounce limit.
+ *
+ * d_offsets: n + 1 words, the exclusive scan of len; d_offsets[n] is the true
+ * total even when it exceeds cap (it fits 32 bits: RT_RAYS_MAX bounds the
+ * records).  All n + 1 words hold their values when the call completes,
+ * nothing past them is written; no clearing needed.  d_records, d_coef and
+ * d_terms may each be NULL.  Vertex v of ray i has index j = d_offsets[i] + v
+ * and is written iff j < cap: nothing at or past cap is written.  With all
+ * three NULL the call only counts and cap is ignored.  Per written vertex:
+ *     d_records[j]      an rt_gsample (8-byte aligned): P, N and obj are the
+ *                       hit record's bits; prim = RT_PATH_PRIM (the hit records
+ *                       do not keep the triangle; the consumers read the sign
+ *                       only); queries = v; dist = +0
+ *     d_coef[j]         the record's coef: 1 for vertex 0, then the product of
+ *                       the nr of the objects before it (cpu/raytracer.c:29)
+ *     d_terms[3j..3j+2] the record's shaded term, under the lights and
+ *                       materials of the batch
+ * The terms fold to the batch's colours: color_add from (+0, +0, +0) over a
+ * ray's terms, deepest first, is d_rgb of that ray, word for word
+ * (rtgpu.path_fold).  The records chain hop by hop: a ray cast from P_v along
+ * ray_bounce(d_v, N_v) (cpu/ray.c:16-25) has vertex v + 1 as its first hit.
+ * Without an overflow rt_stats.hit_records of the batch is the total: a
+ * caller sizes cap from it without a second call.
+ *
+ * To the context: the call reads only (calling it again gives the same
+ * words), asynchronous on `stream`, which must be the batch's stream.  The
+ * paths survive what the kept frame survives (rt_hip_occluded,
+ * rt_hip_ambient_occlusion, rt_hip_ao_rays, rt_hip_direct_light,
+ * rt_hip_frame_rays, rt_hip_stats) and also rt_hip_set_lights and
+ * rt_hip_set_materials (the terms stay the batch's own).  They are gone after
+ * anything that writes or moves hit records: rt_hip_render,
+ * rt_hip_render_compat, a ray cast or a newer batch (which replaces them),
+ * rt_hip_gather, rt_hip_set_triangles, any reallocation of the hit buffers.
+ * After RT_EHITBUF the call exports what the fold saw -- its terms still fold
+ * to what that batch wrote to d_rgb -- and the caller traces again as before.
+ *
+ * RT_EINVAL with nothing written and nothing changed: a NULL context; a
+ * context left broken by a failed geometry update; no such batch kept (the
+ * message names the call that took it); n other than the batch's; NULL
+ * d_offsets; d_records not 8-byte aligned; another stream. */
+#define RT_PATH_PRIM 0x7fffffff   /* a hit whose triangle the hit records do not keep */
+int rt_hip_path_records(rt_hip_ctx *ctx, size_t n, unsigned *d_offsets, size_t cap,
+                        void *d_records, float *d_coef, float *d_terms, void *stream);
+/* Allocate, rt_hip_path_records on the batch's stream, download (offsets
+ * whole, the arrays up to min(total, cap) vertices), synchronise. */
+int rt_hip_path_records_host(rt_hip_ctx *ctx, size_t n, unsigned *h_offsets, size_t cap,
+                             rt_gsample *h_records, float *h_coef, float *h_terms);
+
 /* gpu/rt compatibility mode (gpu/raytracer.cu:31-129,
  * gpu/light.cu, gpu/colors.cu): the camera's frame rendered at 3x width and
  * height with one ray per high-resolution pixel, uint8 saturating colours,

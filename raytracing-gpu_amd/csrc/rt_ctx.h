@@ -14,6 +14,8 @@
 //   rt_occl.cpp    rt_hip_occluded: a caller's occlusion batches
 //   rt_ao.cpp      rt_hip_ambient_occlusion: occlusion counts per G-buffer record
 //   rt_dlight.cpp  rt_hip_direct_light: direct light per G-buffer record
+//   rt_gather.cpp  rt_hip_gather: traced light over a record's hemisphere
+//   rt_paths.cpp   rt_hip_path_records: the last ray batch's paths written out
 // Internal, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -90,6 +92,19 @@ struct StreamOwner {
   StreamOwner(const StreamOwner&) = delete;
   ~StreamOwner() { if (s) (void)hipStreamDestroy(s); }
   operator hipStream_t() const { return s; }
+};
+
+// The ray batch whose paths are still in the hit-record buffers (rt_hip_ctx::paths)
+struct KeptPaths {
+  size_t n = 0;                  // the batch's rays
+  hipStream_t stream = nullptr;  // the stream it ran on
+  int valid = 0;
+  const char* taken_by = nullptr;  // while !valid: the call that took them (nullptr: no batch yet)
+  void keep(size_t rays, hipStream_t s) { n = rays, stream = s, valid = 1, taken_by = nullptr; }
+  void drop(const char* by) {
+    if (valid) taken_by = by;
+    valid = 0;
+  }
 };
 
 struct rt_hip_ctx {
@@ -175,6 +190,12 @@ struct rt_hip_ctx {
   int lb_proven = -1;               // built proven (exact_shadows) or slack-grown
   unsigned long long lb_entry_cap = 0;  // test hook: fail builds past this many entries (0: none)
   int last_batch = 0;               // the last launch was a ray batch (rt_hip_trace_rays): rt_hip_stats reports rays, no list
+  // the paths rt_hip_path_records exports (csrc/rt_paths.cpp): those of the
+  // last rt_hip_trace_rays that traced with a colour output, while nothing has
+  // written or moved hit records since (last_p's hit views are that batch's).
+  // Whoever does says so with drop(its name): the refusal names it
+  KeptPaths paths;
+  DevBuf<uint32_t> d_path_tot;      // the export's block totals (csrc/rt_path_items.h rt_path_scratch_words)
   // occlusion batches and their kin (csrc/rt_batch.h) count into a stats
   // block of their own (the layout of d_stats): the render's trace-side
   // counters, which a relight keeps, stay as they are.  last_occl: the last

@@ -31,6 +31,7 @@ extern "C" int rt_hip_gather(rt_hip_ctx* c, const void* d_samples, size_t n, uns
   c->gb_valid = 0;
   c->rl_valid = 0;
   c->relight.invalidate();
+  c->paths.drop("rt_hip_gather");
   KParams p = scene_params(c);
   p.tile_counter = c->d_counter;
   p.stats = c->d_stats;

@@ -589,6 +589,7 @@ int hit_buffers(rt_hip_ctx* c, size_t items, bool capture) {
   c->d_hit_term.reset();
   c->d_hit_lit.reset();
   c->relight.invalidate();
+  c->paths.drop("a reallocation of the hit buffers");
   const size_t n = want * RT_HIT_REGIONS;
   HIP_TRY(c->d_hit.alloc(2 * n));
   HIP_TRY(c->d_hit_prev.alloc(n));
@@ -896,6 +897,7 @@ extern "C" int rt_hip_render(rt_hip_ctx* c, const rt_frame* f, int rank, int nra
   if (rc) return rc;
   c->gb_valid = 0;
   c->rl_valid = 0;
+  c->paths.drop("rt_hip_render");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   // lists rt_hip_cand_consume built for exactly this frame and rank: used once
@@ -1197,6 +1199,7 @@ static int geometry_forget(rt_hip_ctx* c) {
   c->rl_valid = 0;
   c->gb_valid = 0;
   c->relight.invalidate();
+  c->paths.drop("rt_hip_set_triangles");
   c->last_batch = 0;
   c->last_occl = 0;
   c->last_async = 0;
@@ -1579,6 +1582,7 @@ extern "C" int rt_hip_render_compat(rt_hip_ctx* c, const rt_camera* cam, unsigne
   c->last_batch = 0;
   c->last_occl = 0;
   c->rl_valid = 0;         // (and no hit records are kept: nothing to relight)
+  c->paths.drop("rt_hip_render_compat");
   c->relight.invalidate();
   if (hipMemsetAsync(c->d_counter, 0, kFrameCounterBytes, s) != hipSuccess ||
       rt_launch_compat(&p, accel, c->grid, s) != hipSuccess ||

@@ -357,6 +357,31 @@ extern "C" hipError_t rt_launch_gather_trace(const KParams* p, const GatherArgs*
                                              hipStream_t stream);
 extern "C" hipError_t rt_gather_grid(int accel, int wide, int cus, int* grid);
 extern "C" hipError_t rt_launch_gather_fold(const KParams* p, const GatherArgs* a, hipStream_t stream);
+// The path export (rt_hip_path_records, csrc/rt_paths.hip, a translation unit
+// of its own): the kept batch's hit-record buffers in, the caller's arrays
+// out.  Three launches on 256-ray blocks (csrc/rt_path_items.h), none waiting
+// for another workgroup: every ray's chain length into offsets[i] and every
+// block's total into btot; one workgroup scanning btot in place and writing
+// offsets[n]; the block-local scan that turns the lengths into offsets, and
+// each chain walked again and stored first hit first below cap.
+struct PathArgs {
+  const float4* hit;         // the batch's KParams::hit, hit_prev, hit_term, last, hit_cap
+  const uint32_t* hit_prev;
+  const float4* hit_term;
+  const uint32_t* last;
+  uint32_t hit_cap;
+  uint32_t nblocks;          // rt_path_blocks(n)
+  unsigned long long n;      // rays
+  unsigned long long cap;    // vertices the output arrays hold
+  uint32_t* offsets;         // n + 1 words
+  uint32_t* btot;            // rt_path_scratch_words(n): block totals, then block bases
+  uint2* records;            // five 8-byte pairs per vertex (rt_gsample), or NULL
+  float* coef;               // one per vertex, or NULL
+  float* terms;              // three per vertex, or NULL
+};
+extern "C" hipError_t rt_launch_path_lengths(const PathArgs* a, hipStream_t stream);
+extern "C" hipError_t rt_launch_path_totals(const PathArgs* a, hipStream_t stream);
+extern "C" hipError_t rt_launch_path_write(const PathArgs* a, hipStream_t stream);
 // persistent grid (one-wave workgroups) of trace (trace = 1) or shade on `cus` CUs
 extern "C" hipError_t rt_render_grid(int trace, int accel, int count_work, int policy, int cus,
                                      int* grid);

@@ -30,6 +30,7 @@ extern "C" int rt_hip_trace_rays(rt_hip_ctx* c, const float* d_origins, const fl
   c->gb_valid = 0;
   c->rl_valid = 0;
   c->relight.invalidate();
+  c->paths.drop(d_rgb ? "a newer rt_hip_trace_rays" : "a ray cast (rt_hip_trace_rays without d_rgb)");
   KParams p = scene_params(c);
   p.tile_counter = c->d_counter;
   p.stats = c->d_stats;
@@ -89,6 +90,7 @@ extern "C" int rt_hip_trace_rays(rt_hip_ctx* c, const float* d_origins, const fl
   c->last_batch = 1;
   c->last_occl = 0;
   c->last_stream = s;
+  if (!cast) c->paths.keep(n, s);  // rt_hip_path_records exports this batch's paths
   return RT_OK;
 }
 

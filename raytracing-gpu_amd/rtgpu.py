@@ -245,6 +245,10 @@ _PROTOS = [
                                 C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]),
     ("rt_hip_gather_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_ulonglong, C.c_uint, C.c_void_p,
                                      C.c_uint, C.c_uint, C.c_uint, C.c_void_p, C.POINTER(Stats)]),
+    ("rt_hip_path_records", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    ("rt_hip_path_records_host", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     ("rt_hip_direct_light", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
                                       C.c_void_p]),
     ("rt_hip_direct_light_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p,
@@ -867,6 +871,85 @@ def gather_sum(colours, k):
     return acc
 
 
+# ---- a ray batch's paths (include/rt_hip.h rt_hip_path_records) ----
+RT_PATH_PRIM = 0x7fffffff
+
+
+def _color_add(acc, c):
+    """color_add of cpu/colors.c in float32: one add per channel, then `if (x >
+    255) x = 255` (a NaN passes the compare)."""
+    f = np.float32
+    acc = (acc + c).astype(f)
+    return np.where(acc > f(255), f(255), acc)
+
+
+def path_fold(offsets, terms):
+    """The numpy float32 twin of a ray batch's fold over exported paths
+    (Context.path_records): offsets (n + 1,), terms (total, 3) -> (n, 3)
+    float32, per ray acc = color_add(acc, term_v) from (+0, +0, +0) over its
+    vertices deepest first (v = len - 1 .. 0), as cpu/raytracer.c:29-30 sums
+    from the deepest call outwards.  An empty path gives +0 +0 +0."""
+    f = np.float32
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    t = np.ascontiguousarray(terms, dtype=f).reshape(-1, 3)
+    n = len(off) - 1
+    assert n >= 0 and (n == 0 or (np.diff(off) >= 0).all()) and off[0] == 0 and off[-1] <= len(t)
+    ln = np.diff(off)
+    acc = np.zeros((n, 3), f)
+    with np.errstate(all="ignore"):
+        for d in range(int(ln.max()) if n else 0):
+            on = np.nonzero(ln > d)[0]
+            acc[on] = _color_add(acc[on], t[off[on + 1] - 1 - d])
+    return acc
+
+
+def color_mul(c, coef):
+    """color_mul of cpu/colors.c in float32: init_color(c / 255 * coef) per
+    channel -- the quotient, the product, times 255, then `if (y > 255) y =
+    255; if (y < 0) y = 0` (a NaN and -0.0 pass both compares).  c (n, 3),
+    coef scalar or (n,) -> (n, 3) float32."""
+    f = np.float32
+    c = np.ascontiguousarray(c, dtype=f).reshape(-1, 3)
+    k = np.broadcast_to(np.asarray(coef, dtype=f).reshape(-1, 1), (len(c), 1))
+    with np.errstate(all="ignore"):
+        y = (((c / f(255)).astype(f) * k).astype(f) * f(255)).astype(f)
+        y = np.where(y > f(255), f(255), y)
+        y = np.where(y < f(0), f(0), y)
+    return y.astype(f)
+
+
+def bounce_dir(d, N):
+    """ray_bounce of cpu/ray.c:16-25 in float32, in the device's operation
+    order (csrc/rt_device.h bounce_dir): d - N * (2 * ((N.x d.x + N.y d.y) + N.z
+    d.z)), N used as given.  (n, 3), (n, 3) -> (n, 3) float32."""
+    f = np.float32
+    d = np.ascontiguousarray(d, dtype=f).reshape(-1, 3)
+    N = np.ascontiguousarray(N, dtype=f).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        p = (N * d).astype(f)
+        dot = ((p[:, 0] + p[:, 1]).astype(f) + p[:, 2]).astype(f)
+        s = (f(2) * dot).astype(f)
+        return (d - (s[:, None] * N).astype(f)).astype(f)
+
+
+def path_coefs(offsets, records, nr):
+    """The coefficients of exported paths from their records alone: coef_0 = 1,
+    coef_{v+1} = nr[obj_v] * coef_v in float32 (cpu/raytracer.c:29), nr = the
+    objects' reflection coefficients (Scene.materials_array()[:, 11]) ->
+    float32 (total,)."""
+    f = np.float32
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    r = np.ascontiguousarray(records, dtype=GSAMPLE).reshape(-1)
+    nr = np.asarray(nr, dtype=f).reshape(-1)
+    ln = np.diff(off)
+    out = np.zeros(len(r), f)
+    with np.errstate(all="ignore"):
+        for v in range(int(ln.max()) if len(ln) else 0):
+            j = off[:-1][ln > v] + v
+            out[j] = f(1) if v == 0 else (nr[r["obj"][j - 1]] * out[j - 1]).astype(f)
+    return out
+
+
 # ---- direct light for caller's records (include/rt_hip.h rt_hip_direct_light) ----
 def records_from_points(P, N, obj, prim=0):
     """GSAMPLE records for Context.direct_light from caller points: (n, 3)
@@ -938,6 +1021,7 @@ class Context:
     """One device image of a scene (rt_hip_create); renders through the C ABI."""
 
     RT_EINEXACT = -11
+    _batch_n = _batch_records = 0  # the last trace_rays with colours: its rays and rt_stats.hit_records
 
     def __init__(self, scene: Scene, accel="octree", device=0):
         self.device = device
@@ -1332,10 +1416,13 @@ class Context:
         smp = np.zeros(len(o), GSAMPLE) if samples else None
         st = Stats()
         self.last_rc = 0  # the call's return code (RT_EINEXACT passes _check_render after a parity-breaking knob)
-        self._check_render(self._keep_rc(lib().rt_hip_trace_rays_host(
+        rc = self._keep_rc(lib().rt_hip_trace_rays_host(
             self.h, o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), len(o),
             RT_RAYS_PACKET if packet else 0, rgb.ctypes.data_as(C.c_void_p) if shade else None,
-            smp.ctypes.data_as(C.c_void_p) if samples else None, C.byref(st))), "rt_hip_trace_rays_host")
+            smp.ctypes.data_as(C.c_void_p) if samples else None, C.byref(st)))
+        if shade and len(o):  # what path_records sizes its arrays by
+            self._batch_n, self._batch_records = len(o), int(st.hit_records)
+        self._check_render(rc, "rt_hip_trace_rays_host")
         return rgb, smp, st.as_dict()
 
     def frame_rays(self, frame, order="pixel"):
@@ -1435,6 +1522,57 @@ class Context:
             len(tab), int(seed) & 0xffffffff, RT_RAYS_PACKET if packet else 0, rgb.ctypes.data_as(C.c_void_p),
             C.byref(st))), "rt_hip_gather_host")
         return rgb, st.as_dict()
+
+    def path_records_device(self, n, d_offsets, cap=0, d_records=0, d_coef=0, d_terms=0, stream=None):
+        """rt_hip_path_records on device pointers (asynchronous, on the
+        batch's stream): the paths of the last ray batch with colours, n its
+        rays.  d_offsets receives n + 1 uint32; below `cap` vertices d_records
+        receives GSAMPLE records, d_coef one float and d_terms three floats per
+        vertex; 0 leaves any of the three out (all three: a count)."""
+        _check(lib().rt_hip_path_records(
+            self.h, int(n), C.c_void_p(d_offsets) if d_offsets else None, int(cap),
+            C.c_void_p(d_records) if d_records else None, C.c_void_p(d_coef) if d_coef else None,
+            C.c_void_p(d_terms) if d_terms else None, C.c_void_p(stream) if stream else None),
+            "rt_hip_path_records")
+
+    def path_records(self, records=True, coef=True, terms=True, n=None, cap=None):
+        """The paths of the last ray batch with colours (rt_hip_path_records_host)
+        -> (offsets (n + 1,) uint32, GSAMPLE records (total,), coef (total,)
+        float32, terms (total, 3) float32; None for what was not asked).  n and
+        cap default to the rays and rt_stats.hit_records of the last
+        trace_rays / trace_paths of this object; the arrays are checked against
+        offsets[n] and cut to it (an overflowing batch counts more records than
+        its paths hold).  cap given: at most cap vertices, as the C call."""
+        if n is None:
+            n = self._batch_n
+        fit = cap is None
+        if fit:
+            cap = self._batch_records
+        n, cap = int(n), int(cap)
+        off = np.zeros(n + 1, np.uint32)
+        for _ in range(2):
+            rec = np.zeros(cap, GSAMPLE) if records else None
+            cf = np.zeros(cap, np.float32) if coef else None
+            tm = np.zeros((cap, 3), np.float32) if terms else None
+            _check(lib().rt_hip_path_records_host(
+                self.h, n, off.ctypes.data_as(C.c_void_p), cap,
+                rec.ctypes.data_as(C.c_void_p) if records else None, cf.ctypes.data_as(C.c_void_p) if coef else None,
+                tm.ctypes.data_as(C.c_void_p) if terms else None), "rt_hip_path_records_host")
+            total = int(off[n])
+            if not fit or total <= cap or not (records or coef or terms):
+                break
+            cap = total  # (the export reads only: the same words again, all of them)
+        k = min(total, cap)
+        cut = lambda a: None if a is None else a[:k]
+        return off, cut(rec), cut(cf), cut(tm)
+
+    def trace_paths(self, origins, dirs, packet=False):
+        """trace_rays and the batch's paths in one go -> (rgb (n, 3) float32,
+        offsets (n + 1,) uint32, GSAMPLE records (total,), coef (total,), terms
+        (total, 3), stats): path_fold(offsets, terms) is rgb."""
+        rgb, _, st = self.trace_rays(origins, dirs, packet=packet)
+        off, rec, cf, tm = self.path_records()
+        return rgb, off, rec, cf, tm, st
 
     def direct_light_device(self, d_samples, n, d_rgb, d_lit=0, packet=False, stream=None):
         """rt_hip_direct_light on device pointers (asynchronous): d_samples = n
